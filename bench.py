@@ -41,6 +41,8 @@ CONFIG5_PARITY_FILE = os.path.join(ROOT, "profiles", "config5_parity.json")   # 
 DOMINANT_SOURCES = {"bf16": ("svpc_amd/csrc/gemm_p8.hip", "svpc_amd/csrc/gemm_common.h", "svpc_amd/csrc/common.h"),
                     "bf16x3": ("svpc_amd/csrc/gemm_p8x3.hip", "svpc_amd/csrc/gemm_common.h", "svpc_amd/csrc/common.h")}
 HBM_PEAK_TBPS = 8.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (≈6.3 achievable)
+DUMP_MAX_BYTES = 64 << 20    # --dump-outputs: the whole dump
+DUMP_SAMPLE, DUMP_SEED = 1 << 22, 0     # --dump-outputs: sampled gradient / weight elements (16 MB each in float32), fixed seed
 
 
 def dominant_kernel_sha(precision="bf16"):
@@ -170,6 +172,10 @@ def parse_args(argv=None):
                     help="also time the oracle with one thread per PHYSICAL core of the box when that exceeds this process's CPU share "
                          "(measured on the round-3 box: 128 threads on a 16-CPU share = 59.9 s/step against 7.55 s/step with 16 — oversubscribed, so off by default)")
     ap.add_argument("--parity-steps", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB): train — loss, global gradient norm, per-parameter gradient and weight norms, a fixed seeded "
+                         "sample of the gradients and updated weights; --decode — the greedy token ids")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher/rendezvous check without a GPU: every rank joins the process group, SUM-all-reduces a small CPU "
                          "gradient arena through GradReducer and rank 0 prints the JSON line (tests/test_bench_launcher.py)")
@@ -396,7 +402,42 @@ def cpu_baseline(cfg, model, args, threads=None, warmup=None, steps=None):
                       % (n_vid, args.batch, args.clips, args.layers, warmup, len(times), dt, scaled)}
 
 
-def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup):
+def _save_outputs(dump_dir, arrays):
+    """{name: float32 / float64 ndarray} → dump_dir/<name>.npy"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "output dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+
+
+def dump_train_outputs(dump_dir, opt, loss):
+    """What the last timed train step hands its caller: the loss, and the gradients and updated parameters it leaves behind.  Every
+    trained tensor contributes its gradient and weight norm (float64); the elements themselves as one fixed, seeded sample of
+    DUMP_SAMPLE positions.  Tensors are taken in parameter-name order, so the files do not depend on the arena's layout."""
+    import numpy as np
+    import torch
+    arena = opt.ensure_built()
+    params = [p for _, p in sorted(zip(arena.names, arena.params), key=lambda e: e[0])]
+    with torch.no_grad():
+        grads = torch.cat([p.grad.reshape(-1) for p in params])
+        weights = torch.cat([p.detach().reshape(-1) for p in params])
+        n = grads.numel()
+        pick = (np.arange(n) if n <= DUMP_SAMPLE else
+                np.unique(np.random.RandomState(DUMP_SEED).randint(0, n, size=DUMP_SAMPLE)))
+        pick_d = torch.from_numpy(pick).to(grads.device)
+        out = {"loss": np.array([float(loss)], np.float64),
+               "grad_global_norm": np.array([float(opt.grad_norm())], np.float64),
+               "grad_norms": torch.stack([p.grad.double().norm() for p in params]).cpu().numpy(),
+               "weight_norms": torch.stack([p.detach().double().norm() for p in params]).cpu().numpy(),
+               "grad_sample": grads[pick_d].float().cpu().numpy(),
+               "weight_sample": weights[pick_d].float().cpu().numpy()}
+    _save_outputs(dump_dir, out)
+
+
+def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup, dump_dir=None):
     """captions/s of Translator.translate_batch (greedy) on synthetic clips, videos sharded over ranks (replicas only)."""
     import torch
     from svpc_amd import make_batch, synthetic as syn
@@ -428,6 +469,9 @@ def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup):
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir is not None and rank == 0:
+        # the last timed call's greedy ids, one (clips, Lt) block per video in batch order (ids < 2^24: exact in float32)
+        _save_outputs(dump_dir, {"decode_ids": torch.cat(out).float().cpu().numpy()})
     caps = world * steps * n_vid * args.clips
     # roofline of the decode, from ONE eager call bracketed with HIP events at its two phase boundaries (after the timed region; the
     # timed calls replay a hipGraph, inside which events cannot be recorded): encoder side (clip encoder over n_vid·S clips, step
@@ -527,7 +571,7 @@ def ragged_batches(cfg, args, device, n_structs, seed=4242, shared_features=Fals
     return out, clips
 
 
-def run_train(args, precision, device, world, rank, dist, steps, warmup, instrument=True, ragged=0):
+def run_train(args, precision, device, world, rank, dist, steps, warmup, instrument=True, ragged=0, dump_dir=None):
     """Build model + optimizer in ``precision``, warm up, capture, time ``steps`` steps.  → dict (rank-0 view)."""
     import torch
     from svpc_amd import ops, synthetic as syn
@@ -623,6 +667,8 @@ def run_train(args, precision, device, world, rank, dist, steps, warmup, instrum
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if dump_dir is not None and rank == 0:
+        dump_train_outputs(dump_dir, opt, loss)      # before any later leg steps the model again
     # exposed exchange time: the same steps with the all-reduce calls skipped (gradients stay local — timing only, after the
     # timed region); difference of the two = what the exchange adds to a step after overlap
     no_exchange_ms = None
@@ -846,7 +892,8 @@ def worker(args):
         if args.decode:
             ops.set_precision(args.precision)
             cfg, model = build(args, device)
-            out = run_decode(cfg, model, args, device, world, rank, dist if world > 1 else None, args.steps, args.warmup)
+            out = run_decode(cfg, model, args, device, world, rank, dist if world > 1 else None, args.steps, args.warmup,
+                             dump_dir=args.dump_outputs)
             if rank == 0:
                 print(json.dumps(out))
         else:
@@ -859,7 +906,8 @@ def _train_main(args, device, world, rank, dist, joined):
     import torch
     from svpc_amd import ops
     r = run_train(args, args.precision, device, world, rank, dist, args.steps, args.warmup,
-                  ragged=(args.ragged if (world == 1 and not args.rehearse_dp and not args.no_secondary) else 0))
+                  ragged=(args.ragged if (world == 1 and not args.rehearse_dp and not args.no_secondary) else 0),
+                  dump_dir=args.dump_outputs)
     cfg, gsum = r["cfg"], r["gsum"]
     extras = {}
     if world == 1 and not args.no_secondary and not args.rehearse_dp:

@@ -57,3 +57,18 @@ def test_single_gpu_line_has_the_contract_fields(precision):
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic", "attention")) <= set(rec["roofline"])
     assert rec["config"]["mode"] == precision
     assert "AccumulateGrad node's stream does not match" not in err
+
+
+@pytest.mark.timeout(290)
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """``--dump-outputs DIR``: the arrays of the last timed step as float32 / float64 .npy files within 64 MB; the loss is the
+    line's final_loss, the per-tensor gradient norms add up to the global norm the step clipped with"""
+    import numpy as np
+    rec, _ = _bench("--dump-outputs", str(tmp_path))
+    z = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(z) == {"loss", "grad_global_norm", "grad_norms", "weight_norms", "grad_sample", "weight_sample"}
+    assert all(a.dtype in (np.float32, np.float64) for a in z.values())
+    assert sum(a.nbytes for a in z.values()) <= 64 << 20
+    assert float(z["loss"][0]) == pytest.approx(rec["config"]["final_loss"], rel=1e-6)
+    assert np.all(np.isfinite(z["grad_norms"])) and z["grad_norms"].max() > 0 and np.all(np.isfinite(z["weight_sample"]))
+    np.testing.assert_allclose(float(z["grad_global_norm"][0]), float(np.sqrt((z["grad_norms"] ** 2).sum())), rtol=1e-3)

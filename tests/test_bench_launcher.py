@@ -61,3 +61,36 @@ def test_committed_parity_records_are_readable_whether_fresh_or_stale(monkeypatc
             assert b is None or isinstance(b, dict)
             if fresh:
                 assert a and "loss_rel_vs_oracle_worst" in a and b and "token_agreement_vs_oracle" in b
+
+
+def test_dump_outputs_helper_writes_float_arrays_in_name_order(tmp_path, monkeypatch):
+    """``--dump-outputs``: the train step's loss, gradient / weight norms per tensor (taken in parameter-name order, not arena order)
+    and one seeded sample of the gradient and weight elements, all float32 / float64 and within the 64 MB cap; the sample is the
+    same positions from run to run."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    g = torch.Generator().manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(30, 40, generator=g)), torch.nn.Parameter(torch.randn(7, generator=g))]
+    for p in params:
+        p.grad = torch.randn(p.shape, generator=g)
+    arena = types.SimpleNamespace(names=["z.weight", "a.bias"], params=params)
+    opt = types.SimpleNamespace(ensure_built=lambda: arena, grad_norm=lambda: torch.tensor(3.0))
+    for d in ("a", "b"):
+        bench.dump_train_outputs(str(tmp_path / d), opt, torch.tensor(1.5))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grad_global_norm.npy", "grad_norms.npy", "grad_sample.npy", "loss.npy", "weight_norms.npy", "weight_sample.npy"]
+    z = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in z.values())
+    assert sum(a.nbytes for a in z.values()) <= bench.DUMP_MAX_BYTES
+    assert z["loss"].tolist() == [1.5] and z["grad_global_norm"].tolist() == [3.0]
+    np.testing.assert_allclose(z["grad_norms"], [float(params[1].grad.norm()), float(params[0].grad.norm())], rtol=1e-6)
+    np.testing.assert_allclose(z["weight_norms"], [float(params[1].detach().norm()), float(params[0].detach().norm())], rtol=1e-6)
+    flat_g = torch.cat([params[1].grad.reshape(-1), params[0].grad.reshape(-1)]).numpy()
+    assert 0 < z["grad_sample"].size <= 1000 and np.isin(z["grad_sample"], flat_g).all()
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
