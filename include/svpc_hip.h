@@ -227,6 +227,14 @@ int svpc_attn_q1_ln_supported(int D, int dh, int n_keys, int ldq, int ldkv, int 
 int svpc_attn_q1_ln_fwd(const float* Q, int ldq, float* K, float* V, int ldkv, int k_stride, int n_keys, const float* newK, const float* newV,
                         int ldnew, const float* X, int ldx, const float* gamma, const float* beta, float eps, float* O, int ldo, int T, int D,
                         int dh, float scale, svpc_stream_t stream);
+/* the same block for beam search (src/translator.py:194-203, `--use_beam --beam_size`, src/test.py:207-209), over T = sentences × B
+ * hypothesis rows: with key_rows ((T, ld_rows) int32, the ancestry table svpc_beam_step writes) query t attends to rows key_rows[t·ld_rows + j],
+ * j < n_keys, of K / V, and newK / newV are first stored at key_rows[t·ld_rows + n_keys − 1] — each hypothesis reads its ancestors' rows
+ * where they were written, the caches are never copied or reordered.  key_rows == NULL: query t reads rows (t / q_group)·k_stride + j
+ * (the B hypotheses of a sentence share its memory rows in the cross-attention).  Same shape limits as svpc_attn_q1_ln_fwd. */
+int svpc_attn_q1_ln_idx_fwd(const float* Q, int ldq, float* K, float* V, int ldkv, int k_stride, int n_keys, const int* key_rows, int ld_rows,
+                            int q_group, const float* newK, const float* newV, int ldnew, const float* X, int ldx, const float* gamma,
+                            const float* beta, float eps, float* O, int ldo, int T, int D, int dh, float scale, svpc_stream_t stream);
 int svpc_attn_bwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, const float* O, int ldo,
                   const float* LSE, const float* dO, int lddo, float* dQ, int lddq, float* dK, int lddk, float* dV, int lddv,
                   float* delta, const int* seq, int n_seq, int H, int dh, int max_q, int max_k, const float* key_mask, int causal,
@@ -475,6 +483,21 @@ int svpc_greedy_pick(const float* scores, int ld, const int* row_c, const int* r
  * (text_out: model-side ids, ext_out: extended ids; src/translator.py:96-99 writes them at the top of the next iteration) */
 int svpc_greedy_pick_append(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int lt, int pos, int unk,
                             int* next_ext, int* next_model, int* text_out, int* ext_out, int ld_out, int col, svpc_stream_t stream);
+/* beam-search decoding step (src/translator.py:194-203 accepts `use_beam`; src/test.py:207-209 defines --use_beam / --beam_size): one
+ * workgroup per sentence over its `beam` hypothesis rows r = t·beam + h of `scores` (row r: its first row_c[r] columns, the last row_x[r] of
+ * them copied OOV words).  logits == 0: scores are probabilities p, step score log p (p <= 0: −inf); logits != 0: step score = logit − the
+ * log-sum-exp of the row.  The UNK column is not a candidate.  Candidates rank by higher cum_parent + step, then higher raw value, then
+ * lower parent·C + column; a finished hypothesis offers only itself (token pad, step 0).  In place: cum, finished (a child is finished once
+ * its extended id is eos).  Out: parent (global parent row), next_ext / next_model (OOV → unk on the model side), and the ping-pong tables
+ * (T·beam, ld_tok): text / ext ids and the KV-cache ancestry rows_out[r][j] = rows_in[parent][j] for j <= pos, rows_out[r][pos + 1] =
+ * r·slot_rows + pos + 1 (the hypothesis's own cache slot).  No host synchronisation, fixed buffers: graph-capture safe. */
+int svpc_beam_step(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                   int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                   int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, svpc_stream_t stream);
+/* end of the beam decode: per sentence the hypothesis with the highest cum (ties: the lowest index), its first lt ids of `ext`
+ * ((n_sent·beam, ld_tok)) into best_ids ((n_sent, lt)) and its cum into best_score */
+int svpc_beam_finalize(const float* cum, const int* ext, int ld_tok, int n_sent, int beam, int lt, int* best_ids, float* best_score,
+                       svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

@@ -315,6 +315,9 @@ struct Q1LnArgs {
     const float* newK; const float* newV; int ldnew;
     const float* X; int ldx; const float* gamma; const float* beta; float eps; float* O; int ldo;
     int T, D; float scale;
+    // indexed form (svpc_attn_q1_ln_idx_fwd, beam search): key / value row j of query t is rows[t·ld_rows + j] (the new row is stored at
+    // rows[t·ld_rows + n_keys − 1]); without a table the rows are (t / group)·k_stride + j — `group` queries share one sentence's rows
+    const int* rows; int ld_rows; int group;
 };
 // 16 bytes of the key / value cache with the non-temporal hint: the cache (up to 104 MB per layer and iteration) is read once per
 // iteration and must not push the decoder's weights (71 MB, re-read every iteration) out of the Infinity Cache
@@ -327,14 +330,16 @@ __device__ __forceinline__ float row16_sum(float v) {
     v = dpp_add_<0xB1>(v); v = dpp_add_<0x4E>(v); v = dpp_add_<0x141>(v); v = dpp_add_<0x140>(v);
     return v;
 }
-template <int MAXK>
+template <int MAXK, bool IDX = false>
 __global__ __launch_bounds__(256) void attn_q1_ln_kernel(Q1LnArgs a) {
     __shared__ float red[2][4];
     const int t = blockIdx.x, tid = threadIdx.x, d0 = 4 * tid;
     const int nw = blockDim.x >> 6;
     const bool app = a.newK != nullptr;
     const int nc = app ? a.n_keys - 1 : a.n_keys;                   // rows read from the cache
-    const size_t row0 = (size_t)t * a.k_stride;
+    const size_t row0 = IDX ? (size_t)(t / a.group) * a.k_stride : (size_t)t * a.k_stride;
+    const int* rt = IDX && a.rows ? a.rows + (size_t)t * a.ld_rows : nullptr;
+    auto krow = [&](int j) -> size_t { return IDX && rt ? (size_t)rt[j] : row0 + j; };
     float4 q = *reinterpret_cast<const float4*>(a.Q + (size_t)t * a.ldq + d0);
     const float4 xr = *reinterpret_cast<const float4*>(a.X + (size_t)t * a.ldx + d0);
     const float4 gm = *reinterpret_cast<const float4*>(a.gamma + d0), bt = *reinterpret_cast<const float4*>(a.beta + d0);
@@ -346,7 +351,7 @@ __global__ __launch_bounds__(256) void attn_q1_ln_kernel(Q1LnArgs a) {
     float4 kr[MAXK];
 #pragma unroll
     for (int j = 0; j < MAXK; ++j)      // (rows past the end re-read the last one — unconditional loads, all in flight; nc == 0 reads row 0 of the sentence's own cache block)
-        kr[j] = q1_stream4(a.K + (row0 + min(j, max(nc - 1, 0))) * a.ldkv + d0);
+        kr[j] = q1_stream4(a.K + krow(min(j, max(nc - 1, 0))) * a.ldkv + d0);
     q.x *= a.scale; q.y *= a.scale; q.z *= a.scale; q.w *= a.scale;
     float sc[MAXK], sn = -INFINITY, mx = -INFINITY;
 #pragma unroll
@@ -358,12 +363,12 @@ __global__ __launch_bounds__(256) void attn_q1_ln_kernel(Q1LnArgs a) {
     float4 vr[MAXK];
 #pragma unroll
     for (int j = 0; j < MAXK; ++j)
-        vr[j] = q1_stream4(a.V + (row0 + min(j, max(nc - 1, 0))) * a.ldkv + d0);
+        vr[j] = q1_stream4(a.V + krow(min(j, max(nc - 1, 0))) * a.ldkv + d0);
     if (app) {
         sn = row16_sum(q.x * kn.x + q.y * kn.y + q.z * kn.z + q.w * kn.w);
         mx = fmaxf(mx, sn);
-        *reinterpret_cast<float4*>(a.K + (row0 + nc) * a.ldkv + d0) = kn;
-        *reinterpret_cast<float4*>(a.V + (row0 + nc) * a.ldkv + d0) = vn;
+        *reinterpret_cast<float4*>(a.K + krow(nc) * a.ldkv + d0) = kn;
+        *reinterpret_cast<float4*>(a.V + krow(nc) * a.ldkv + d0) = vn;
     }
     float l = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -441,6 +446,30 @@ int svpc_attn_q1_ln_fwd(const float* Q, int ldq, float* K, float* V, int ldkv, i
     else if (nc <= 24) hipLaunchKernelGGL(attn_q1_ln_kernel<24>, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(attn_q1_ln_kernel<32>, grid, block, 0, stream, a);
     return svpc_check_launch("attn_q1_ln_fwd");
+}
+// the same block for beam search (T = sentences × beam hypothesis rows).  key_rows (T, ld_rows) int32: query t attends to the rows
+// key_rows[t·ld_rows + j], j < n_keys, of K / V, and with newK / newV its own row is first stored at key_rows[t·ld_rows + n_keys − 1] — a
+// hypothesis reads its ancestors' cache rows in place, nothing is copied.  key_rows == nullptr: query t reads rows (t / q_group)·k_stride + j
+// (the B hypotheses of a sentence share its memory rows in the cross-attention).
+int svpc_attn_q1_ln_idx_fwd(const float* Q, int ldq, float* K, float* V, int ldkv, int k_stride, int n_keys, const int* key_rows, int ld_rows,
+                            int q_group, const float* newK, const float* newV, int ldnew, const float* X, int ldx, const float* gamma,
+                            const float* beta, float eps, float* O, int ldo, int T, int D, int dh, float scale, hipStream_t stream) {
+    if (T == 0) return 0;
+    SVPC_REQUIRE(svpc_attn_q1_ln_supported(D, dh, n_keys, ldq, ldkv, newK ? ldnew : 0, ldx, ldo) == 1 && (newK == nullptr) == (newV == nullptr) &&
+                     (key_rows ? ld_rows >= n_keys : (q_group >= 1 && k_stride >= n_keys)) &&
+                     ((((uintptr_t)Q) | ((uintptr_t)K) | ((uintptr_t)V) | ((uintptr_t)newK) | ((uintptr_t)newV) | ((uintptr_t)X) | ((uintptr_t)gamma) |
+                       ((uintptr_t)beta) | ((uintptr_t)O)) & 15) == 0,
+                 "attn_q1_ln_idx: needs heads of 64, D % 256 == 0, D <= 1024, 1..32 key rows per query, ld_rows >= n_keys, 16-byte aligned rows");
+    Q1LnArgs a{Q, ldq, K, V, ldkv, k_stride, n_keys, newK, newV, ldnew, X, ldx, gamma, beta, eps, O, ldo, T, D, scale, key_rows, ld_rows,
+               key_rows ? 1 : q_group};
+    const int nc = newK ? n_keys - 1 : n_keys;
+    const dim3 grid(T), block(D / 4);
+    if (nc <= 4) hipLaunchKernelGGL((attn_q1_ln_kernel<4, true>), grid, block, 0, stream, a);
+    else if (nc <= 8) hipLaunchKernelGGL((attn_q1_ln_kernel<8, true>), grid, block, 0, stream, a);
+    else if (nc <= 16) hipLaunchKernelGGL((attn_q1_ln_kernel<16, true>), grid, block, 0, stream, a);
+    else if (nc <= 24) hipLaunchKernelGGL((attn_q1_ln_kernel<24, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((attn_q1_ln_kernel<32, true>), grid, block, 0, stream, a);
+    return svpc_check_launch("attn_q1_ln_idx_fwd");
 }
 
 int svpc_attn_fwd(const float* Q, int ldq, const float* K, int ldk, const float* V, int ldv, float* O, int ldo, float* LSE,

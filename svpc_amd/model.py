@@ -321,23 +321,34 @@ class BertDecoderLayerNoMemoryUntied(nn.Module):
         wkv, bkv, _, _, _ = self.dec_enc_attention.packed("kv")
         return ops.linear(mem, wkv, bkv)
 
-    def step(self, x, pos, lt, cache, mem_kv, seq_self, seq_cross, cx):
+    def step(self, x, pos, lt, cache, mem_kv, seq_self, seq_cross, cx, key_rows=None, q_group=1):
         """The layer for ONE new token per sentence (position ``pos``): its K|V row is appended to ``cache`` ((T·lt, 2D), sentence-
         major), the query attends to the pos+1 cached keys (the causal mask of the reference, model.py:630-640, lets position
-        ``pos`` see exactly those), then cross-attention to the precomputed memory K|V and the output block."""
+        ``pos`` see exactly those), then cross-attention to the precomputed memory K|V and the output block.
+        Beam search: the T rows are hypotheses (``q_group`` per sentence, sharing its ``mem_kv`` rows) and ``key_rows`` ((T, ≥ pos+1)
+        int32, ``ops.beam_step``'s ancestry table) names the cache rows of each one's positions 0 … pos — its own row ``pos`` is written
+        to its own slot, nothing else of the cache moves.  ``seq_self`` / ``seq_cross`` then segment the fallback's gathered key rows
+        (T sequences of pos+1) and the T queries over their sentence's memory rows."""
         T, D = x.shape
         w, b, _, _, _ = self.self_attention.packed()
         qkv = ops.linear(x, w, b)
         # cache append + one-query attention + residual + LayerNorm in one launch where the shape allows (fp32 rows, heads of 64)
-        x1 = ops.attn_q1_ln(qkv, cache, lt, pos + 1, x, self.norm1.weight, self.norm1.bias, cx.eps, cx.H, new_kv=qkv[:, D:])
+        beam = {} if key_rows is None else dict(key_rows=key_rows)        # (without a table: the greedy call, unchanged)
+        x1 = ops.attn_q1_ln(qkv, cache, lt, pos + 1, x, self.norm1.weight, self.norm1.bias, cx.eps, cx.H, new_kv=qkv[:, D:], **beam)
         if x1 is None:
             cache.view(T, lt, 2 * D)[:, pos].copy_(qkv[:, D:])
-            sa = ops.attention(qkv, cache, (0, 0, D), D, cx.H, seq_self, key_mask=None, causal=False)
+            keys = cache
+            if key_rows is not None:        # (shapes the fused kernel declines: the ancestors' rows gathered, then the generic attention)
+                idx = key_rows[:, :pos + 1].reshape(-1).contiguous()
+                keys = torch.empty(T * (pos + 1), 2 * D, dtype=cache.dtype, device=cache.device)
+                ops._rows_move(cache, None, idx, keys, None, keys.shape[0], 2 * D)
+            sa = ops.attention(qkv, keys, (0, 0, D), D, cx.H, seq_self, key_mask=None, causal=False)
             x1 = ops.layernorm(sa, self.norm1.weight, self.norm1.bias, cx.eps, residual=x)
         ca_m = self.dec_enc_attention
         qc = ops.linear(x1, ca_m.query.weight, ca_m.query.bias)
-        n_mem = mem_kv.shape[0] // T
-        x2 = ops.attn_q1_ln(qc, mem_kv, n_mem, n_mem, x1, self.norm2.weight, self.norm2.bias, cx.eps, cx.H)
+        n_mem = mem_kv.shape[0] // (T // q_group)
+        x2 = ops.attn_q1_ln(qc, mem_kv, n_mem, n_mem, x1, self.norm2.weight, self.norm2.bias, cx.eps, cx.H,
+                            **({} if q_group == 1 else dict(q_group=q_group)))
         if x2 is None:
             ca = ops.attention(qc, mem_kv, (0, 0, D), D, cx.H, seq_cross, key_mask=None, causal=False)
             x2 = ops.layernorm(ca, self.norm2.weight, self.norm2.bias, cx.eps, residual=x1)

@@ -1476,13 +1476,22 @@ class _SplitCols(Function):
         return g, None, None
 
 
-def attn_q1_ln(q, kv, k_stride, n_keys, residual, gamma, beta, eps, n_heads, new_kv=None):
+def attn_q1_ln(q, kv, k_stride, n_keys, residual, gamma, beta, eps, n_heads, new_kv=None, key_rows=None, q_group=1):
     """One decoding step of an attention block (reference decoder layer model.py:620-663 for one new position per sentence,
     translator.py:88-112): LayerNorm(residual + Attention(q; the sentence's key / value rows)), one launch.  ``q``: (T, ≥D) fp32, the
     query in its first D columns; ``kv``: (rows, 2D) fp32, K | V, sentence t owning rows t·k_stride … t·k_stride + n_keys − 1;
     ``new_kv`` (T, 2D view): the token's own K | V, stored as the sentence's row n_keys − 1 first (the cache append).  Forward only.
+    Beam search (svpc_attn_q1_ln_idx_fwd): ``key_rows`` ((T, ≥ n_keys) int32, the ancestry table of ``beam_step``) names the kv rows of
+    query t — the new row goes to key_rows[t, n_keys − 1]; without a table, ``q_group`` > 1 lets queries t read the rows of t // q_group.
     Returns None when the shape is not taken (the caller then runs copy / attention / layernorm separately)."""
     T, D = residual.shape
+    indexed = key_rows is not None or q_group != 1
+    if key_rows is not None:
+        if not (key_rows.dtype == torch.int32 and key_rows.is_contiguous() and key_rows.dim() == 2 and key_rows.shape[0] == T
+                and key_rows.shape[1] >= n_keys and key_rows.device == residual.device):
+            raise ValueError("attn_q1_ln: key_rows must be a contiguous int32 (T, >= n_keys) table on the rows' device")
+    elif q_group != 1 and (q_group < 1 or T % q_group or kv.shape[0] < (T // q_group) * k_stride):
+        raise ValueError("attn_q1_ln: q_group must divide T and the kv rows must cover T / q_group sentences")
     if torch.is_grad_enabled() and (q.requires_grad or residual.requires_grad):
         return None
     ts = (q, kv, residual) + ((new_kv,) if new_kv is not None else ())
@@ -1496,6 +1505,12 @@ def attn_q1_ln(q, kv, k_stride, n_keys, residual, gamma, beta, eps, n_heads, new
         return None
     out = torch.empty(T, D, dtype=torch.float32, device=q.device)
     nk = new_kv.data_ptr() if new_kv is not None else None
+    if indexed:
+        _lib.call("attn_q1_ln_idx_fwd", _p(q), q.stride(0), kv.data_ptr(), kv.data_ptr() + 4 * D, kv.stride(0), k_stride, n_keys, _p(key_rows),
+                  key_rows.shape[1] if key_rows is not None else 0, int(q_group), nk, (nk + 4 * D) if nk is not None else None, ldn,
+                  _p(residual), residual.stride(0), _p(gamma), _p(beta), float(eps), _p(out), D, T, D, D // n_heads, 1.0 / math.sqrt(D // n_heads),
+                  _stream())
+        return out
     _lib.call("attn_q1_ln_fwd", _p(q), q.stride(0), kv.data_ptr(), kv.data_ptr() + 4 * D, kv.stride(0), k_stride, n_keys, nk,
               (nk + 4 * D) if nk is not None else None, ldn, _p(residual), residual.stride(0), _p(gamma), _p(beta), float(eps), _p(out), D, T, D,
               D // n_heads, 1.0 / math.sqrt(D // n_heads), _stream())
@@ -2503,3 +2518,52 @@ def greedy_pick(scores, row_c, row_x, lt, pos, unk, append=None):
     _lib.call("greedy_pick", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), n, lt, int(pos),
               int(unk), _p(ext), _p(mod), _stream())
     return ext, mod
+
+
+BEAM_MAX = 8
+
+
+def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows):
+    """One beam-search selection step (svpc_beam_step) over ``scores`` (T·beam, ≥ C) — probabilities, or logits when ``logits``.
+    ``cum`` (T·beam,) fp32 and ``finished`` (T·beam,) int32 are updated in place; ``toks_in`` / ``toks_out`` = (text, ext, key_rows): the
+    ping-pong (T·beam, Lt) int32 id matrices and KV-cache ancestry tables, the children's written for positions ≤ pos + 1.
+    → (parent, next_ext, next_model) int32 (T·beam,)."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_step: beam width must be 1..%d" % BEAM_MAX)
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("beam_step: scores must be fp32 (T·beam, C) rows with unit column stride")
+    if not (cum.dtype == torch.float32 and finished.dtype == torch.int32 and finished.shape == cum.shape and cum.is_contiguous()
+            and finished.is_contiguous()):
+        raise ValueError("beam_step: cum fp32 and finished int32, both contiguous (T·beam,)")
+    lt = toks_in[0].shape[1]
+    for m in tuple(toks_in) + tuple(toks_out):
+        if m.dtype != torch.int32 or not m.is_contiguous() or tuple(m.shape) != (R, lt) or m.device != scores.device:
+            raise ValueError("beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
+    if not 0 <= pos < lt - 1 or slot_rows < lt:
+        raise ValueError("beam_step: position %d outside the %d-column tables" % (pos, lt))
+    _need_gpu(scores)
+    dev = scores.device
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("beam_step", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
+              1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
+              _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt), _stream())
+    return parent, nxt_ext, nxt
+
+
+def beam_finalize(cum, ext, beam):
+    """→ (ids (T, Lt) int32, score (T,) fp32): per sentence the hypothesis of highest ``cum`` (ties: lowest index) — svpc_beam_finalize."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_finalize: beam width must be 1..%d" % BEAM_MAX)
+    R, lt = ext.shape
+    if (R % beam or cum.shape != (R,) or cum.dtype != torch.float32 or ext.dtype != torch.int32 or not ext.is_contiguous()
+            or not cum.is_contiguous()):
+        raise ValueError("beam_finalize: cum fp32 (T·beam,) and ext int32 (T·beam, Lt), contiguous")
+    _need_gpu(ext)
+    T = R // beam
+    ids = torch.empty(T, lt, dtype=torch.int32, device=ext.device)
+    score = torch.empty(T, dtype=torch.float32, device=ext.device)
+    _lib.call("beam_finalize", _p(cum), _p(ext), lt, T, int(beam), lt, _p(ids), _p(score), _stream())
+    return ids, score

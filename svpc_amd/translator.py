@@ -1,4 +1,4 @@
-"""Greedy caption decoding on the MI355X — drop-in for the reference's ``Translator`` (src/translator.py:27-228).
+"""Greedy and beam-search caption decoding on the MI355X — drop-in for the reference's ``Translator`` (src/translator.py:27-228).
 
 Same constructor and ``translate_batch`` contract (12-element ``model_inputs`` list in, ``(dec_seq_list, oov_word_dict)``
 out, one ``(S_b, Lt)`` int64 id matrix per video, extended ids ≥ V kept for copied OOV words).  Restructured for the GPU:
@@ -11,6 +11,27 @@ per-layer cache and attends to the i+1 cached keys; cross-attention K|V of the m
 are computed once.  Under the reference's causal∧pad mask (translator.py:88-100 re-runs all Lt positions every iteration) position
 i's output depends on exactly those keys, so the ids are the same — ``incremental=False`` keeps the re-run-everything form, and
 the parity tests check both against the reference's ids.
+
+**Beam search** (``translate_batch(model_inputs, use_beam=True)``, width ``B = opt.beam_size`` (default 2, 1 ≤ B ≤ 8), the reference
+CLI's ``--use_beam --beam_size``, test.py:207-209 → translate.py:73-74, which the reference's own Translator accepts and ignores).  Returns
+what greedy returns; ``translate_batch_beam(model_inputs, beam_size)`` also returns one fp32 score per sentence.  The contract:
+
+- the encoder side runs once per batch; the decoding iterations run over T·B hypothesis rows (hypothesis-major within a sentence);
+- step score of a token: pointer modes ``log p`` of the mixed extended-vocabulary probability (p ≤ 0: −inf); ``video`` mode the
+  ``log_softmax`` of the logits over the row's columns; the UNK column is never a candidate;
+- hypothesis score: the fp32 sum ``cum_child = cum_parent + step``, no length penalty;
+- position 0 is BOS; the Lt − 1 picks of positions 1 … Lt − 1 are selected and scored (greedy's last, discarded iteration has no
+  counterpart); at the first step only beam 0 is alive (initial scores [0, −inf, …]);
+- candidates rank by higher cum, then higher raw value (p, or the logit), then lower flat index parent·C + column — so B = 1 picks what
+  greedy picks;
+- a hypothesis whose extended id is EOS is finished: from then on its only candidate is itself with token PAD (both id spaces), step
+  score 0; rows hold PAD after EOS (the reference's ``convert_ids_to_sentence`` stops at the first EOS and drops PAD);
+- copied OOV words keep their extended id ≥ V in the output, the model side sees UNK;
+- the result per sentence is the best of the B final hypotheses by cum (ties: the lowest beam index);
+- ``incremental=False`` raises NotImplementedError; ``two_streams`` is ignored.
+
+The per-layer KV caches hold one slot of Lt rows per hypothesis; a row is written once, into the slot of the hypothesis that computes it,
+and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that the attention reads through (no cache copy per step).
 """
 from __future__ import annotations
 
@@ -18,8 +39,8 @@ import torch
 
 from . import ops
 from .model import BatchPlan, _Ctx
-from .ops_common import ACT_RELU, Idx
-from .synthetic import BOS, PAD, UNK
+from .ops_common import ACT_RELU, Idx, SeqInfo
+from .synthetic import BOS, EOS, PAD, UNK
 
 
 class Translator(object):
@@ -65,14 +86,31 @@ class Translator(object):
         return input_ids, input_masks
 
     def translate_batch(self, model_inputs, use_beam=False, recurrent=True, untied=False, xl=False, mtrans=False):
+        if use_beam:
+            dec, oov, _ = self.translate_batch_beam(model_inputs, getattr(self.opt, "beam_size", 2))
+            return dec, oov
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
          ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
         return self.translate_batch_greedy(input_ids_list, video_features_list, input_masks_list, token_type_ids_list,
                                            ingr_input_ids, ingr_masks, ingr_sep_masks, ingr_id_dict, oov_word_dict,
                                            alignments, actions, batch_step_num, self.model)
 
+    @torch.no_grad()
+    def translate_batch_beam(self, model_inputs, beam_size):
+        """Beam search of width ``beam_size`` (module docstring) → (dec_seq_list, oov_word_dict, score_list): per video an (S_b, Lt)
+        int64 id matrix, as greedy, and an (S_b,) fp32 tensor of the chosen hypotheses' summed step scores."""
+        B = int(beam_size)
+        if not 1 <= B <= ops.BEAM_MAX:
+            raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, beam_size))
+        if not self.incremental:
+            raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
+         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
+        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids,
+                               ingr_sep_masks, ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=B)
+
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
-    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev):
+    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0):
         cfg = model.config
         mode = cfg.model_mode
         Lt, V = cfg.max_t_len, cfg.vocab_size
@@ -80,7 +118,7 @@ class Translator(object):
         dicts = ingr_id_dict if mode != "video" else [{}] * N
         n_oov = [len(d) if mode != "video" else 0 for d in oov_word_dict]
         key = (tuple(int(v) for v in batch_step_num), sep_t.numpy().tobytes(), tuple(n_oov), S_pad, N, L, str(dev), self.incremental,
-               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts))
+               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts), beam)
         prep = self._preps.get(key)
         if prep is not None:
             return prep
@@ -92,7 +130,12 @@ class Translator(object):
                     pl=model._ptr_plan(dicts, c_list, Lt, plan.step_ne, plan.row_vid),
                     row_x=Idx([n_oov[b] for b in plan.row_vid.host]),
                     pl1=model._ptr_plan(dicts, c_list, 1, plan.step_ne, plan.step_vid),
-                    row_x1=Idx([n_oov[b] for b in plan.step_vid.host]), seq_cross={}, graph=None)
+                    row_x1=Idx([n_oov[b] for b in plan.step_vid.host]), seq_cross={}, graph=None, beam=beam)
+        if beam:
+            # hypothesis rows t·B + h: the pointer plan of B rows per sentence (ptr_attn_gate / ptr_mix_loss with lt = B)
+            row_vid = Idx([b for b in plan.step_vid.host for _ in range(beam)])
+            prep.update(plb=model._ptr_plan(dicts, c_list, beam, plan.step_ne, row_vid), row_xb=Idx([n_oov[b] for b in row_vid.host]),
+                        seq_self_b={})
         if len(self._preps) > 32:
             self._preps.clear()
         self._preps[key] = prep
@@ -152,6 +195,10 @@ class Translator(object):
             bank = None
 
         stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
+        if prep["beam"]:
+            out = self._beam_iterations(model, prep, mem, bank, cx, tab=self._text_table(model, Lt, cx, dev))
+            stamp()
+            return out
         text = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
         ext = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
         nxt = torch.full((T,), BOS, dtype=torch.int32, device=dev)
@@ -203,10 +250,62 @@ class Translator(object):
         stamp()
         return text if mode == "video" else ext
 
+    def _beam_iterations(self, model, prep, mem, bank, cx, tab):
+        """The Lt − 1 selection steps of a beam decode over the T·B hypothesis rows → (ids (T, Lt) int32, score (T,) fp32)."""
+        cfg = model.config
+        mode = cfg.model_mode
+        B, T = prep["beam"], prep["T"]
+        TB = T * B
+        dev = mem.device
+        Lt, D = cfg.max_t_len, cfg.hidden_size
+        n_mem = mem.shape[0] // T
+        layers = model.decoder.layer
+        caches = [torch.zeros(TB * Lt, 2 * D, dtype=torch.float32, device=dev) for _ in layers]     # one slot of Lt rows per hypothesis
+        st = model.decoder.stacked_memory_kv()
+        if st is not None:
+            mem_kv = ops.split_cols(ops.linear(mem, st[0], st[1]), len(layers))
+        else:
+            mem_kv = [layer.memory_kv(mem) for layer in layers]
+        proj = model.bank_projection(bank) if bank is not None else None
+        key = ("beam", n_mem)
+        seq_cross = prep["seq_cross"].get(key)
+        if seq_cross is None:          # (the fallback's segmentation: hypothesis r over the memory rows of its sentence r // B)
+            seq_cross = prep["seq_cross"][key] = SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, dev)
+        plb, row_xb = prep["plb"], prep["row_xb"]
+        # ping-pong (text ids, extended ids, KV-cache ancestry) tables: children are written from their parents' rows
+        toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
+        toks[0][0][:, 0] = BOS
+        toks[0][1][:, 0] = BOS
+        toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
+        cum = torch.zeros(T, B, dtype=torch.float32, device=dev)
+        cum[:, 1:] = float("-inf")                                                 # the first step: beam 0 alone
+        cum = cum.view(TB)
+        fin = torch.zeros(TB, dtype=torch.int32, device=dev)
+        nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
+        for i in range(Lt - 1):
+            t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
+            seq_self = prep["seq_self_b"].get(i)
+            if seq_self is None:
+                seq_self = prep["seq_self_b"][i] = SeqInfo.uniform(TB, 1, i + 1, dev)
+            x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
+            for layer, cache, kv in zip(layers, caches, mem_kv):
+                x = layer.step(x, i, Lt, cache, kv, seq_self, seq_cross, cx, key_rows=t_in[2], q_group=B)
+            if mode == "video":
+                scores = model.decoder_classifier.run(x, cx.eps)          # raw logits: the step score is their log_softmax
+            else:
+                scores, _ = model._lm_probs(x, bank, plb, cx, proj=proj)
+            _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt)
+        return ops.beam_finalize(cum, toks[(Lt - 1) % 2][1], B)
+
     @torch.no_grad()
     def translate_batch_greedy(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list,
                                ingr_input_ids, ingr_masks, ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions,
                                batch_step_num, rt_model):
+        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
+                               ingr_id_dict, oov_word_dict, batch_step_num, rt_model)
+
+    def _translate(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
+                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0):
         model = rt_model
         dev = video_features_list[0].device
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
@@ -232,7 +331,7 @@ class Translator(object):
         def part(lo, hi, stream=None):
             n = hi - lo
             prep = self._prepare(model, list(batch_step_num[lo:hi]), sep_all[lo:hi], list(ingr_id_dict[lo:hi]), list(oov_word_dict[lo:hi]),
-                                 S_pad, n, L, dev)
+                                 S_pad, n, L, dev, beam=beam)
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
                 out = self._decode_core(model, prep, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
@@ -246,7 +345,7 @@ class Translator(object):
         # independent (the reference decodes them one by one, translator.py:175-191), so the ids are those of the unsplit decode bit for
         # bit (tests/test_config5_gpu.py).  Two replayed graphs on two streams, not one forked graph.
         halves = [(0, N)]
-        if self.graph and self.two_streams and dev.type == "cuda" and N >= 2 * self.min_half:
+        if self.graph and self.two_streams and not beam and dev.type == "cuda" and N >= 2 * self.min_half:
             halves = [(0, N // 2), (N // 2, N)]
         if len(halves) == 1:
             plans_outs = [part(0, N)]
@@ -262,12 +361,19 @@ class Translator(object):
                     plans_outs.append(part(lo, hi, st))
             for st in (sa, sb):
                 cur.wait_stream(st)
-        res = []
+        res, scores = [], []
         for plan, out in plans_outs:
+            score = None
+            if beam:
+                out, score = out
             out = out.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
                 o, n_ = plan.h_step_off[b], plan.h_step_len[b]
                 res.append(out[o:o + n_])
+                if beam:
+                    scores.append(score[o:o + n_])
+        if beam:
+            return res, oov_word_dict, scores
         return res, oov_word_dict
 
     def _decode_graphed(self, model, prep, src, shape, stream=None):
@@ -324,4 +430,4 @@ class Translator(object):
         for dst, s_ in zip(static, src):
             dst.copy_(s_)
         graph.replay()
-        return out.clone()
+        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()

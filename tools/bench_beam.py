@@ -1,0 +1,93 @@
+"""Beam-search decode throughput at BASELINE config 5 (64 videos × 12 clips, vivt, D = 768, L = 6; bf16x3 by default, hipGraph replay):
+captions/s of Translator.translate_batch for greedy and for beam widths 1, 2, 4 on the same batch, with the encoder-side and per-iteration
+milliseconds of one eager call bracketed by HIP events (an upper bound on the replayed phases).  Prints one JSON line.
+
+    python tools/bench_beam.py [--steps 10] [--warmup 2] [--videos 64] [--precision bf16x3] [--widths 1,2,4] [--profile-width 4]
+
+With --profile-width B only one replayed decode of width B runs (for rocprofv3 --kernel-trace --stats)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--videos", type=int, default=64)
+    ap.add_argument("--clips", type=int, default=12)
+    ap.add_argument("--precision", default="bf16x3", choices=["bf16", "bf16x3", "fp32"])
+    ap.add_argument("--widths", default="1,2,4")
+    ap.add_argument("--profile-width", type=int, default=0)
+    a = ap.parse_args(argv)
+    import torch
+    import bench
+    from svpc_amd import make_batch, ops, synthetic as syn
+    from svpc_amd.translator import Translator
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    stream = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(stream):
+        ops.set_precision(a.precision)
+        args = bench.parse_args([])
+        cfg, model = bench.build(args, dev)
+        b = make_batch(cfg, n_videos=a.videos, max_steps=a.clips, n_ingr=10, n_oov=0, seed=2019, full_clips=True)
+        b["_ingr_host_lists"] = (b["ingr_input_ids"].tolist(), b["ingr_masks"].tolist(), b["ingr_sep_masks"].tolist())
+        for k, v in list(b.items()):
+            if isinstance(v, list) and v and isinstance(v[0], torch.Tensor):
+                b[k] = [t.to(dev) for t in v]
+            elif isinstance(v, torch.Tensor):
+                b[k] = v.to(dev)
+        O = type("O", (), {"cuda": True})
+        tr = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=True)
+
+        def call(tr_, width):
+            if width == 0:
+                return tr_.translate_batch(syn.translate_inputs(b))
+            return tr_.translate_batch_beam(syn.translate_inputs(b), width)
+
+        if a.profile_width:
+            call(tr, a.profile_width)                  # eager warm-up twice + capture
+            torch.cuda.synchronize()
+            call(tr, a.profile_width)                  # the replayed decode
+            torch.cuda.synchronize()
+            print(json.dumps({"profiled": "one replayed beam decode", "beam": a.profile_width, "videos": a.videos}))
+            return
+        legs = {}
+        caps = a.videos * a.clips
+        for width in [0] + [int(w) for w in a.widths.split(",") if w]:
+            for _ in range(max(1, a.warmup)):
+                call(tr, width)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                call(tr, width)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            tr_e = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=False)
+            call(tr_e, width)
+            tr_e.phase_events = []
+            call(tr_e, width)
+            torch.cuda.synchronize()
+            e = tr_e.phase_events
+            n_it = cfg.max_t_len - (1 if width else 0)
+            enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+            legs["greedy" if width == 0 else "beam%d" % width] = {
+                "captions_per_s": caps * a.steps / el, "ms_per_batch": 1000.0 * el / a.steps,
+                "eager_encoder_side_ms": enc_ms, "eager_iterations": n_it, "eager_ms_per_iteration": dec_ms / n_it}
+        g = legs["greedy"]["captions_per_s"]
+        for k, v in legs.items():
+            v["vs_greedy"] = v["captions_per_s"] / g
+        print(json.dumps({"metric": "beam-search decode captions/sec (config 5)", "videos": a.videos, "clips": a.clips,
+                          "precision": a.precision, "launch": "hipGraph replay per batch structure and width", "steps": a.steps,
+                          "legs": legs}))
+
+
+if __name__ == "__main__":
+    main()
