@@ -498,6 +498,22 @@ int svpc_beam_step(const float* scores, int ld, const int* row_c, const int* row
  * ((n_sent·beam, ld_tok)) into best_ids ((n_sent, lt)) and its cum into best_score */
 int svpc_beam_finalize(const float* cum, const int* ext, int ld_tok, int n_sent, int beam, int lt, int* best_ids, float* best_score,
                        svpc_stream_t stream);
+/* svpc_beam_step with the decoding controls of the reference's OpenNMT-derived decoder lineage (min_length, block_ngram_repeat,
+ * exclusion_tokens, length_penalty; src/train.py:548 and src/test.py:209 parse --n_best).  All off (0 / NULL) it is svpc_beam_step.
+ * min_len m: eos is not a candidate while pos + 1 <= m.  ngram n > 0 (needs ld_tok <= 64): candidate (h, w) is skipped when the gram
+ * (ext_in[h][pos + 2 − n … pos], w) already occurs in ext_in[h][1 … pos] and none of its ids is set in excl (a bitmap of excl_v ids; ids
+ * >= excl_v, copied OOV words, are never excluded).  Skipped columns stay in the log-sum-exp of logits mode.  lp (NULL: none) is a length
+ * penalty table of ld_tok doubles: candidates rank by (double)cum / lp[len], then the raw value, then the flat index; len (in place,
+ * (T·beam,), needed with lp) is pos + 1 for a live parent's child and kept by a finished one. */
+int svpc_beam_step_ctl(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                       int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                       int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
+                       int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, svpc_stream_t stream);
+/* end of the beam decode, n-best: per sentence its n_best (1 … beam) hypotheses in order of (double)cum / lp[len] (lp NULL: cum), ties to
+ * the lower beam index; their first lt ids of `ext` into best_ids ((n_sent, n_best, lt)), cum into best_score and len into best_len
+ * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */
+int svpc_beam_finalize_nbest(const float* cum, const int* len, const double* lp, const int* ext, int ld_tok, int n_sent, int beam, int lt,
+                             int n_best, int* best_ids, float* best_score, int* best_len, svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

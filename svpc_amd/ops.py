@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import numbers
 import os
 
 import torch
@@ -2523,10 +2524,76 @@ def greedy_pick(scores, row_c, row_x, lt, pos, unk, append=None):
 BEAM_MAX = 8
 
 
-def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows):
+LENGTH_PENALTIES = ("none", "avg", "wu")
+
+
+def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none",
+                        length_penalty_alpha=0.0, n_best=None):
+    """The decoding controls of a beam decode over Lt = ``lt`` positions and ``vocab`` text ids, checked on the host (ValueError) and
+    normalised → dict(block_ngram_repeat, exclusion_tokens (sorted tuple), min_length, length_penalty_name, length_penalty_alpha
+    [, n_best]).  n: 0 … Lt − 1 (and Lt ≤ 64 when n > 0); m: 0 … Lt − 1; exclusion ids in [0, vocab); alpha finite ≥ 0; n_best 1 … beam."""
+    def as_int(name, v):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        return int(v)
+    n = as_int("block_ngram_repeat", block_ngram_repeat)
+    m = as_int("min_length", min_length)
+    if not 0 <= n <= lt - 1:
+        raise ValueError("block_ngram_repeat must be 0..%d (Lt - 1), got %d" % (lt - 1, n))
+    if n > 0 and lt > 64:
+        raise ValueError("block_ngram_repeat needs Lt <= 64 (one wave holds a hypothesis's ids), Lt = %d" % lt)
+    if not 0 <= m <= lt - 1:
+        raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (lt - 1, m))
+    excl = tuple(sorted({as_int("exclusion_tokens", e) for e in (exclusion_tokens or ())}))
+    for e in excl:
+        if not 0 <= e < vocab:
+            raise ValueError("exclusion_tokens must be text ids in [0, %d), got %d" % (vocab, e))
+    name = length_penalty_name if length_penalty_name is not None else "none"
+    if name not in LENGTH_PENALTIES:
+        raise ValueError("length_penalty_name must be one of %s, got %r" % (", ".join(LENGTH_PENALTIES), name))
+    try:
+        alpha = float(length_penalty_alpha)
+    except (TypeError, ValueError):
+        raise ValueError("length_penalty_alpha must be a number, got %r" % (length_penalty_alpha,))
+    if not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("length_penalty_alpha must be finite and >= 0, got %r" % (length_penalty_alpha,))
+    out = dict(block_ngram_repeat=n, exclusion_tokens=excl, min_length=m, length_penalty_name=name, length_penalty_alpha=alpha)
+    if n_best is not None:
+        k = as_int("n_best", n_best)
+        if beam is None or not 1 <= k <= beam:
+            raise ValueError("n_best must be 1..%s (the beam width), got %d" % (beam, k))
+        out["n_best"] = k
+    return out
+
+
+def length_penalty_table(name, alpha, lt):
+    """lp[len] for len = 0 … lt − 1 as float64 (Python floats): ``none`` 1, ``avg`` len, ``wu`` ((5 + len) / 6) ** alpha.  Computed once on
+    the host; the kernels and the CPU reference divide by the same numbers.  (len 0 never ranks: ``avg`` stores 1 there.)"""
+    if name == "none":
+        return [1.0] * lt
+    if name == "avg":
+        return [1.0] + [float(n) for n in range(1, lt)]
+    if name == "wu":
+        return [((5.0 + n) / 6.0) ** float(alpha) for n in range(lt)]
+    raise ValueError("length_penalty_name must be one of %s, got %r" % (", ".join(LENGTH_PENALTIES), name))
+
+
+def exclusion_bitmap(tokens, vocab, device):
+    """(ceil(vocab / 32),) int32: bit t of word t // 32 set for every id t of ``tokens`` (the exclusion set of n-gram blocking)."""
+    words = [0] * ((vocab + 31) // 32)
+    for t in tokens:
+        words[t >> 5] |= 1 << (t & 31)
+    return torch.tensor([w - (1 << 32) if w >= 1 << 31 else w for w in words], dtype=torch.int32, device=device)
+
+
+def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows, *, length=None,
+              min_length=0, block_ngram_repeat=0, exclusion=None, lp=None):
     """One beam-search selection step (svpc_beam_step) over ``scores`` (T·beam, ≥ C) — probabilities, or logits when ``logits``.
     ``cum`` (T·beam,) fp32 and ``finished`` (T·beam,) int32 are updated in place; ``toks_in`` / ``toks_out`` = (text, ext, key_rows): the
     ping-pong (T·beam, Lt) int32 id matrices and KV-cache ancestry tables, the children's written for positions ≤ pos + 1.
+    Decoding controls (keyword-only; any given → svpc_beam_step_ctl): ``length`` (T·beam,) int32 hypothesis lengths, updated in place;
+    ``min_length`` m; ``block_ngram_repeat`` n; ``exclusion`` = (bitmap of ``exclusion_bitmap``, vocab); ``lp`` float64 (Lt,) table of
+    ``length_penalty_table`` (needs ``length``).
     → (parent, next_ext, next_model) int32 (T·beam,)."""
     if not 1 <= beam <= BEAM_MAX:
         raise ValueError("beam_step: beam width must be 1..%d" % BEAM_MAX)
@@ -2542,11 +2609,35 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
             raise ValueError("beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
     if not 0 <= pos < lt - 1 or slot_rows < lt:
         raise ValueError("beam_step: position %d outside the %d-column tables" % (pos, lt))
+    ctl = length is not None or min_length or block_ngram_repeat or exclusion is not None or lp is not None
+    if ctl:
+        if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
+            raise ValueError("beam_step: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
+        if block_ngram_repeat and lt > 64:
+            raise ValueError("beam_step: block_ngram_repeat needs Lt <= 64")
+        if length is not None and (length.dtype != torch.int32 or length.shape != (R,) or not length.is_contiguous()
+                                   or length.device != scores.device):
+            raise ValueError("beam_step: length must be contiguous int32 (T·beam,) on the scores' device")
+        if lp is not None and (length is None or lp.dtype != torch.float64 or lp.dim() != 1 or lp.shape[0] < lt or not lp.is_contiguous()
+                               or lp.device != scores.device):
+            raise ValueError("beam_step: lp must be a contiguous float64 table of >= Lt entries on the scores' device, with length")
+        if exclusion is not None:
+            bits, vocab = exclusion
+            if (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1 or not bits.is_contiguous()
+                    or bits.device != scores.device):
+                raise ValueError("beam_step: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
     _need_gpu(scores)
     dev = scores.device
     parent = torch.empty(R, dtype=torch.int32, device=dev)
     nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
     nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    if ctl:
+        bits, vocab = exclusion if exclusion is not None else (None, 0)
+        _lib.call("beam_step_ctl", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
+                  int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
+                  _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
+                  int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _stream())
+        return parent, nxt_ext, nxt
     _lib.call("beam_step", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
               1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
               _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt), _stream())
@@ -2567,3 +2658,29 @@ def beam_finalize(cum, ext, beam):
     score = torch.empty(T, dtype=torch.float32, device=ext.device)
     _lib.call("beam_finalize", _p(cum), _p(ext), lt, T, int(beam), lt, _p(ids), _p(score), _stream())
     return ids, score
+
+
+def beam_finalize_nbest(cum, ext, beam, n_best, length=None, lp=None):
+    """→ (ids (T, n_best, Lt) int32, score (T, n_best) fp32, len (T, n_best) int32): per sentence its ``n_best`` hypotheses in order of
+    (double)cum / lp[len] (``lp`` None: cum), ties to the lower beam index — svpc_beam_finalize_nbest.  ``length`` (T·beam,) int32 (needed
+    with ``lp``; None: len 0)."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_finalize: beam width must be 1..%d" % BEAM_MAX)
+    if not 1 <= n_best <= beam:
+        raise ValueError("beam_finalize: n_best must be 1..%d, got %r" % (beam, n_best))
+    R, lt = ext.shape
+    if (R % beam or cum.shape != (R,) or cum.dtype != torch.float32 or ext.dtype != torch.int32 or not ext.is_contiguous()
+            or not cum.is_contiguous()):
+        raise ValueError("beam_finalize: cum fp32 (T·beam,) and ext int32 (T·beam, Lt), contiguous")
+    if length is not None and (length.dtype != torch.int32 or length.shape != (R,) or not length.is_contiguous()):
+        raise ValueError("beam_finalize: length must be contiguous int32 (T·beam,)")
+    if lp is not None and (length is None or lp.dtype != torch.float64 or lp.dim() != 1 or lp.shape[0] < lt or not lp.is_contiguous()):
+        raise ValueError("beam_finalize: lp must be a contiguous float64 table of >= Lt entries, with length")
+    _need_gpu(ext)
+    T = R // beam
+    ids = torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device)
+    score = torch.empty(T, n_best, dtype=torch.float32, device=ext.device)
+    ln = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
+    _lib.call("beam_finalize_nbest", _p(cum), _p(length), _p(lp), _p(ext), lt, T, int(beam), lt, int(n_best), _p(ids), _p(score), _p(ln),
+              _stream())
+    return ids, score, ln

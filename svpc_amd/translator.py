@@ -30,6 +30,28 @@ what greedy returns; ``translate_batch_beam(model_inputs, beam_size)`` also retu
 - the result per sentence is the best of the B final hypotheses by cum (ties: the lowest beam index);
 - ``incremental=False`` raises NotImplementedError; ``two_streams`` is ignored.
 
+**Decoding controls** (the reference's OpenNMT-derived decoder lineage: ``min_length``, ``block_ngram_repeat``, ``exclusion_tokens``,
+``length_penalty``, ``n_best``; src/train.py:548 and src/test.py:209 parse ``--n_best``).  Read from ``opt`` with ``getattr`` defaults,
+overridden by keyword arguments of the same names on ``translate_batch``, ``translate_batch_beam`` and ``translate_batch_nbest``; all
+default to off, and with every control off nothing changes (same ids, scores, launches and graphs):
+
+- ``block_ngram_repeat`` n (0: off, ≤ Lt − 1; Lt ≤ 64 when on): a hypothesis's words are its extended ids y_1 … y_pos (BOS excluded;
+  a copied OOV word is its own word).  Candidate (h, w) at position p = pos + 1 ≥ n is banned when its gram (y_{p−n+1} … y_pos, w)
+  equals some earlier (y_j … y_{j+n−1}), j = 1 … p − n, and no token of the gram is in ``exclusion_tokens`` (text ids < V).  The ban is
+  per candidate; banned columns are skipped like UNK (but stay in ``video`` mode's log-sum-exp, so a step score is what it was);
+- ``min_length`` m (0 … Lt − 1): EOS is not a candidate at positions p ≤ m;
+- ``length_penalty_name`` / ``length_penalty_alpha``: candidates rank by key = (double)cum / lp[len], lp = ``none`` 1, ``avg`` len,
+  ``wu`` ((5 + len) / 6) ^ alpha (alpha finite ≥ 0), a float64 table computed once on the host (``ops.length_penalty_table``); a live
+  parent's child has len = p, a finished hypothesis keeps the len at which it picked EOS, one that never finishes ends at Lt − 1.  Order:
+  higher key, then higher raw value, then lower flat index; ``none`` is today's order;
+- fewer than B unbanned candidates in a sentence: the leftover slots are PAD, cum −inf, finished, len = p (as before);
+- the final pick orders a sentence's hypotheses by the final key (ties: the lower beam index); ``translate_batch_beam``'s score is still
+  the fp32 cum; ``translate_batch_nbest(model_inputs, beam_size, n_best)`` (1 ≤ n_best ≤ B, default ``opt.n_best`` = 1) returns
+  ``(dec_seq_list, oov_word_dict, score_list, length_list)``: per video ids (S_b, n_best, Lt) int64, cum (S_b, n_best) fp32 and len
+  (S_b, n_best) int64 in final-key order, so row 0 is ``translate_batch_beam``'s result;
+- greedy (``use_beam=False``) with any control on runs the width-1 beam with those controls; with none, the greedy path is untouched;
+- every argument is checked on the host (ValueError) before any device work.  Each setting has its own prepared plan and captured graph.
+
 The per-layer KV caches hold one slot of Lt rows per hypothesis; a row is written once, into the slot of the hypothesis that computes it,
 and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that the attention reads through (no cache copy per step).
 """
@@ -39,6 +61,7 @@ import torch
 
 from . import ops
 from .model import BatchPlan, _Ctx
+from .ops import check_beam_controls, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
 from .ops_common import ACT_RELU, Idx, SeqInfo
 from .synthetic import BOS, EOS, PAD, UNK
 
@@ -85,9 +108,27 @@ class Translator(object):
         input_masks[text_mask] = 0
         return input_ids, input_masks
 
-    def translate_batch(self, model_inputs, use_beam=False, recurrent=True, untied=False, xl=False, mtrans=False):
+    CONTROLS = dict(block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none", length_penalty_alpha=0.0)
+
+    def _controls(self, kw, beam=None, n_best=None):
+        """The decoding controls: ``opt`` attributes overridden by keyword arguments, checked (ValueError) → (normalised dict, key):
+        key None when every control is off (the uncontrolled decode)."""
+        unknown = set(kw) - set(self.CONTROLS)
+        if unknown:
+            raise TypeError("unknown decoding control(s): %s" % ", ".join(sorted(unknown)))
+        val = {k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.CONTROLS.items()}
+        c = check_beam_controls(self.model_config.max_t_len, self.model_config.vocab_size, beam=beam, n_best=n_best, **val)
+        on = c["block_ngram_repeat"] > 0 or c["min_length"] > 0 or c["length_penalty_name"] != "none"
+        key = (c["block_ngram_repeat"], c["exclusion_tokens"] if c["block_ngram_repeat"] else (), c["min_length"], c["length_penalty_name"],
+               c["length_penalty_alpha"] if c["length_penalty_name"] == "wu" else 0.0) if on else None
+        return c, key
+
+    def translate_batch(self, model_inputs, use_beam=False, recurrent=True, untied=False, xl=False, mtrans=False, **controls):
         if use_beam:
-            dec, oov, _ = self.translate_batch_beam(model_inputs, getattr(self.opt, "beam_size", 2))
+            dec, oov, _ = self.translate_batch_beam(model_inputs, getattr(self.opt, "beam_size", 2), **controls)
+            return dec, oov
+        if self._controls(controls)[1] is not None:        # greedy with controls: the width-1 beam (B = 1 picks what greedy picks)
+            dec, oov, _ = self.translate_batch_beam(model_inputs, 1, **controls)
             return dec, oov
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
          ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
@@ -96,7 +137,7 @@ class Translator(object):
                                            alignments, actions, batch_step_num, self.model)
 
     @torch.no_grad()
-    def translate_batch_beam(self, model_inputs, beam_size):
+    def translate_batch_beam(self, model_inputs, beam_size, **controls):
         """Beam search of width ``beam_size`` (module docstring) → (dec_seq_list, oov_word_dict, score_list): per video an (S_b, Lt)
         int64 id matrix, as greedy, and an (S_b,) fp32 tensor of the chosen hypotheses' summed step scores."""
         B = int(beam_size)
@@ -104,13 +145,32 @@ class Translator(object):
             raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, beam_size))
         if not self.incremental:
             raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        ctl, key = self._controls(controls)
+        res, oov, scores, _ = self._translate_beam(model_inputs, B, ctl, key, 0)
+        return res, oov, scores
+
+    @torch.no_grad()
+    def translate_batch_nbest(self, model_inputs, beam_size=None, n_best=None, **controls):
+        """The ``n_best`` best hypotheses of a width-``beam_size`` beam search (defaults ``opt.beam_size``, ``opt.n_best``; module
+        docstring) → (dec_seq_list, oov_word_dict, score_list, length_list): per video ids (S_b, n_best, Lt) int64, cum (S_b, n_best)
+        fp32 and len (S_b, n_best) int64, rows in final-key order."""
+        B = int(beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2))
+        if not 1 <= B <= ops.BEAM_MAX:
+            raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, beam_size))
+        if not self.incremental:
+            raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        ctl, key = self._controls(controls, beam=B, n_best=n_best if n_best is not None else getattr(self.opt, "n_best", 1))
+        return self._translate_beam(model_inputs, B, ctl, key, ctl["n_best"])
+
+    def _translate_beam(self, model_inputs, B, ctl, key, n_best):
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
          ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
         return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids,
-                               ingr_sep_masks, ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=B)
+                               ingr_sep_masks, ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=B, ctl=(ctl, key),
+                               n_best=n_best)
 
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
-    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0):
+    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0, ctl=None, ranked=False):
         cfg = model.config
         mode = cfg.model_mode
         Lt, V = cfg.max_t_len, cfg.vocab_size
@@ -118,7 +178,8 @@ class Translator(object):
         dicts = ingr_id_dict if mode != "video" else [{}] * N
         n_oov = [len(d) if mode != "video" else 0 for d in oov_word_dict]
         key = (tuple(int(v) for v in batch_step_num), sep_t.numpy().tobytes(), tuple(n_oov), S_pad, N, L, str(dev), self.incremental,
-               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts), beam)
+               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts), beam,
+               ctl[1] if ctl is not None else None, ranked)
         prep = self._preps.get(key)
         if prep is not None:
             return prep
@@ -135,7 +196,16 @@ class Translator(object):
             # hypothesis rows t·B + h: the pointer plan of B rows per sentence (ptr_attn_gate / ptr_mix_loss with lt = B)
             row_vid = Idx([b for b in plan.step_vid.host for _ in range(beam)])
             prep.update(plb=model._ptr_plan(dicts, c_list, beam, plan.step_ne, row_vid), row_xb=Idx([n_oov[b] for b in row_vid.host]),
-                        seq_self_b={})
+                        seq_self_b={}, ranked=ranked)
+            if ranked:
+                # the controls' device tables live as long as the prep: a replayed graph reads the addresses it captured
+                c = ctl[0]
+                n = c["block_ngram_repeat"]
+                prep["ctl"] = dict(
+                    min_length=c["min_length"], block_ngram_repeat=n,
+                    exclusion=(exclusion_bitmap(c["exclusion_tokens"], V, dev), V) if n and c["exclusion_tokens"] else None,
+                    lp=(torch.tensor(length_penalty_table(c["length_penalty_name"], c["length_penalty_alpha"], Lt), dtype=torch.float64,
+                                     device=dev) if c["length_penalty_name"] != "none" else None))
         if len(self._preps) > 32:
             self._preps.clear()
         self._preps[key] = prep
@@ -251,7 +321,8 @@ class Translator(object):
         return text if mode == "video" else ext
 
     def _beam_iterations(self, model, prep, mem, bank, cx, tab):
-        """The Lt − 1 selection steps of a beam decode over the T·B hypothesis rows → (ids (T, Lt) int32, score (T,) fp32)."""
+        """The Lt − 1 selection steps of a beam decode over the T·B hypothesis rows → (ids (T, Lt) int32, score (T,) fp32); with controls
+        or n-best (``prep["ranked"]``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order."""
         cfg = model.config
         mode = cfg.model_mode
         B, T = prep["beam"], prep["T"]
@@ -282,6 +353,9 @@ class Translator(object):
         cum = cum.view(TB)
         fin = torch.zeros(TB, dtype=torch.int32, device=dev)
         nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
+        ranked = prep["ranked"]                   # decoding controls and / or n-best: lengths tracked, the finals sorted by their key
+        ctl = prep.get("ctl")
+        length = torch.zeros(TB, dtype=torch.int32, device=dev) if ranked else None
         for i in range(Lt - 1):
             t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
             seq_self = prep["seq_self_b"].get(i)
@@ -294,7 +368,13 @@ class Translator(object):
                 scores = model.decoder_classifier.run(x, cx.eps)          # raw logits: the step score is their log_softmax
             else:
                 scores, _ = model._lm_probs(x, bank, plb, cx, proj=proj)
-            _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt)
+            if ranked:
+                _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
+                                          length=length, **ctl)
+            else:
+                _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt)
+        if ranked:           # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
+            return ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
         return ops.beam_finalize(cum, toks[(Lt - 1) % 2][1], B)
 
     @torch.no_grad()
@@ -305,9 +385,10 @@ class Translator(object):
                                ingr_id_dict, oov_word_dict, batch_step_num, rt_model)
 
     def _translate(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
-                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0):
+                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0, ctl=None, n_best=0):
         model = rt_model
         dev = video_features_list[0].device
+        ranked = bool(beam) and (n_best > 0 or (ctl is not None and ctl[1] is not None))
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
         # tensors are consecutive slices of one buffer (the usual collate output; model._stacked sees it) that is three launches on the
         # stacked views instead of three per step
@@ -331,7 +412,7 @@ class Translator(object):
         def part(lo, hi, stream=None):
             n = hi - lo
             prep = self._prepare(model, list(batch_step_num[lo:hi]), sep_all[lo:hi], list(ingr_id_dict[lo:hi]), list(oov_word_dict[lo:hi]),
-                                 S_pad, n, L, dev, beam=beam)
+                                 S_pad, n, L, dev, beam=beam, ctl=ctl, ranked=ranked)
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
                 out = self._decode_core(model, prep, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
@@ -361,10 +442,14 @@ class Translator(object):
                     plans_outs.append(part(lo, hi, st))
             for st in (sa, sb):
                 cur.wait_stream(st)
-        res, scores = [], []
+        res, scores, lens = [], [], []
         for plan, out in plans_outs:
-            score = None
-            if beam:
+            score = length = None
+            if ranked:
+                out, score, length = out
+                k = n_best or 1                        # (translate_batch_beam: row 0; translate_batch_nbest: the first n_best rows)
+                out, score, length = (out[:, :k], score[:, :k], length[:, :k].to(torch.int64)) if n_best else (out[:, 0], score[:, 0].contiguous(), None)
+            elif beam:
                 out, score = out
             out = out.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
@@ -372,8 +457,10 @@ class Translator(object):
                 res.append(out[o:o + n_])
                 if beam:
                     scores.append(score[o:o + n_])
+                if length is not None:
+                    lens.append(length[o:o + n_])
         if beam:
-            return res, oov_word_dict, scores
+            return res, oov_word_dict, scores, lens
         return res, oov_word_dict
 
     def _decode_graphed(self, model, prep, src, shape, stream=None):

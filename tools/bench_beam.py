@@ -4,7 +4,10 @@ milliseconds of one eager call bracketed by HIP events (an upper bound on the re
 
     python tools/bench_beam.py [--steps 10] [--warmup 2] [--videos 64] [--precision bf16x3] [--widths 1,2,4] [--profile-width 4]
 
-With --profile-width B only one replayed decode of width B runs (for rocprofv3 --kernel-trace --stats)."""
+Decoding controls (Translator.translate_batch_beam's keywords): --block-ngram N, --min-length M, --length-penalty {none,avg,wu}, --alpha A.
+When any is set, every beam width is timed twice in the same call, without and with them (legs beamB and beamB_ctl, and their ratio).
+
+With --profile-width B only one replayed decode of width B runs (for rocprofv3 --kernel-trace --stats), with the controls if given."""
 import argparse
 import json
 import os
@@ -25,7 +28,13 @@ def main(argv=None):
     ap.add_argument("--precision", default="bf16x3", choices=["bf16", "bf16x3", "fp32"])
     ap.add_argument("--widths", default="1,2,4")
     ap.add_argument("--profile-width", type=int, default=0)
+    ap.add_argument("--block-ngram", type=int, default=0)
+    ap.add_argument("--min-length", type=int, default=0)
+    ap.add_argument("--length-penalty", default="none", choices=["none", "avg", "wu"])
+    ap.add_argument("--alpha", type=float, default=0.0)
     a = ap.parse_args(argv)
+    ctl = dict(block_ngram_repeat=a.block_ngram, min_length=a.min_length, length_penalty_name=a.length_penalty, length_penalty_alpha=a.alpha)
+    ctl_on = a.block_ngram > 0 or a.min_length > 0 or a.length_penalty != "none"
     import torch
     import bench
     from svpc_amd import make_batch, ops, synthetic as syn
@@ -47,46 +56,52 @@ def main(argv=None):
         O = type("O", (), {"cuda": True})
         tr = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=True)
 
-        def call(tr_, width):
+        def call(tr_, width, with_ctl=False):
             if width == 0:
                 return tr_.translate_batch(syn.translate_inputs(b))
-            return tr_.translate_batch_beam(syn.translate_inputs(b), width)
+            return tr_.translate_batch_beam(syn.translate_inputs(b), width, **(ctl if with_ctl else {}))
 
         if a.profile_width:
-            call(tr, a.profile_width)                  # eager warm-up twice + capture
+            call(tr, a.profile_width, ctl_on)          # eager warm-up twice + capture
             torch.cuda.synchronize()
-            call(tr, a.profile_width)                  # the replayed decode
+            call(tr, a.profile_width, ctl_on)          # the replayed decode
             torch.cuda.synchronize()
-            print(json.dumps({"profiled": "one replayed beam decode", "beam": a.profile_width, "videos": a.videos}))
+            print(json.dumps({"profiled": "one replayed beam decode", "beam": a.profile_width, "videos": a.videos,
+                              "controls": ctl if ctl_on else None}))
             return
         legs = {}
         caps = a.videos * a.clips
-        for width in [0] + [int(w) for w in a.widths.split(",") if w]:
+        runs = [(0, False)]
+        for w in [int(w) for w in a.widths.split(",") if w]:
+            runs += [(w, False)] + ([(w, True)] if ctl_on else [])
+        for width, with_ctl in runs:
             for _ in range(max(1, a.warmup)):
-                call(tr, width)
+                call(tr, width, with_ctl)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(a.steps):
-                call(tr, width)
+                call(tr, width, with_ctl)
             torch.cuda.synchronize()
             el = time.perf_counter() - t0
             tr_e = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=False)
-            call(tr_e, width)
+            call(tr_e, width, with_ctl)
             tr_e.phase_events = []
-            call(tr_e, width)
+            call(tr_e, width, with_ctl)
             torch.cuda.synchronize()
             e = tr_e.phase_events
             n_it = cfg.max_t_len - (1 if width else 0)
             enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
-            legs["greedy" if width == 0 else "beam%d" % width] = {
+            legs["greedy" if width == 0 else "beam%d%s" % (width, "_ctl" if with_ctl else "")] = {
                 "captions_per_s": caps * a.steps / el, "ms_per_batch": 1000.0 * el / a.steps,
                 "eager_encoder_side_ms": enc_ms, "eager_iterations": n_it, "eager_ms_per_iteration": dec_ms / n_it}
         g = legs["greedy"]["captions_per_s"]
         for k, v in legs.items():
             v["vs_greedy"] = v["captions_per_s"] / g
+            if k.endswith("_ctl"):
+                v["vs_without_controls"] = v["captions_per_s"] / legs[k[:-len("_ctl")]]["captions_per_s"]
         print(json.dumps({"metric": "beam-search decode captions/sec (config 5)", "videos": a.videos, "clips": a.clips,
-                          "precision": a.precision, "launch": "hipGraph replay per batch structure and width", "steps": a.steps,
-                          "legs": legs}))
+                          "precision": a.precision, "launch": "hipGraph replay per batch structure, width and controls", "steps": a.steps,
+                          "controls": ctl if ctl_on else None, "legs": legs}))
 
 
 if __name__ == "__main__":
