@@ -16,9 +16,13 @@ bar (loss ≤ 1e-4 relative vs the CPU oracle, greedy ids bit-exact: tests/test_
 beside it: ``fastest_mode`` (bf16: bf16 operands and activation streams — faster, but its loss error is > 1e-4; the measured error
 is quoted in the line) and ``parity_mode`` (fp32: f32 MFMA).
 
-Prints ONE JSON line on rank 0: metric/value/… + "roofline" (dominant kernel; + "attention": the clip-encoder attention launches
-against the HBM roofline) + "cpu_baseline" + "secondary" (config 5: greedy decode, with its own roofline) + "fastest_mode" +
-"parity_mode" + "ceilings" (vendor GEMM / copy).
+Prints ONE JSON line on rank 0: metric/value/unit/…/ms_per_step + "config".  A plain run does only what that needs: set up, warm
+up, time the steps, write --dump-outputs, print.  ``--full`` adds, all after the timed region: "roofline" (dominant kernel; +
+"attention": the clip-encoder attention launches against the HBM roofline — three instrumented eager steps of its own when the step
+is replayed from a graph; an eager run brackets its timed steps and prints it either way) + "ragged" + "secondary" (config 5: greedy
+decode, with its own roofline) + "fastest_mode" + "parity_mode" + "padded_text_rows" + "ceilings" (vendor GEMM / copy) +
+"cpu_baseline"; with N > 1 ranks, exchange.ms_per_step_without_exchange.  ``--no-cpu-baseline`` / ``--no-secondary`` / ``--ragged 0``
+trim a --full run.
 """
 import argparse
 import hashlib
@@ -151,8 +155,12 @@ def parse_args(argv=None):
     ap.add_argument("--exchange-dtype", default="fp32", choices=["fp32", "bf16"],
                     help="wire format of the gradient buckets: fp32 (default: N ranks == one process with the N-fold batch, exactly) or "
                          "bf16 (half the xGMI bytes for one 2^-9 rounding per rank; error bounded in tests/test_dp_gloo.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure, after the timed region: roofline, ragged legs, config-5 decode, "
+                         "the other arithmetic modes, the padded sentence layout, ceilings, the CPU baseline (N=1), the exposed exchange "
+                         "time (N>1); --decode: its roofline.  Off by default: a plain run only sets up, warms up, times and prints")
     ap.add_argument("--ragged", type=int, default=20,
-                    help="after the timed region: this many EAGER steps over batches of the structure the reference's loop feeds (S_b ~ U{3..16}, "
+                    help="(--full) after the timed region: this many EAGER steps over batches of the structure the reference's loop feeds (S_b ~ U{3..16}, "
                          "E_b ~ U{1..31}, X_b in {0,1,2}), a different structure every step; printed as the `ragged` field (0 = skip)")
     ap.add_argument("--bucket-timeline", action="store_true",
                     help="record per-bucket issue / completion events of the gradient exchange (exchange.bucket_timeline_ms); ON by default "
@@ -160,10 +168,10 @@ def parse_args(argv=None):
     ap.add_argument("--no-bucket-timeline", action="store_true", help="N > 1: do not record the per-bucket timeline")
     ap.add_argument("--rehearse-dp", action="store_true",
                     help="run the data-parallel code path (process group, three graphs, bucketed all-reduce) even with one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-pack-text", action="store_true",
                     help="run the sentence side over all T x Lt padded rows (default: over the valid tokens only — model.pack_text_rows)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the decode / parity-mode / ceilings legs (N=1 only legs)")
+    ap.add_argument("--no-secondary", action="store_true", help="(--full) skip the ragged / decode / parity-mode / ceilings legs (N=1 only legs)")
     ap.add_argument("--cpu-videos", type=int, default=16, help="videos per CPU-baseline step (16 = the stated configuration)")
     ap.add_argument("--cpu-warmup", type=int, default=3)     # >= 3 warm-up + >= 5 timed steps, median
     ap.add_argument("--cpu-steps", type=int, default=5)
@@ -437,8 +445,9 @@ def dump_train_outputs(dump_dir, opt, loss):
     _save_outputs(dump_dir, out)
 
 
-def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup, dump_dir=None):
-    """captions/s of Translator.translate_batch (greedy) on synthetic clips, videos sharded over ranks (replicas only)."""
+def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup, dump_dir=None, roofline=True):
+    """captions/s of Translator.translate_batch (greedy) on synthetic clips, videos sharded over ranks (replicas only); ``roofline``:
+    also the phase roofline, from two eager calls of its own after the timed region."""
     import torch
     from svpc_amd import make_batch, synthetic as syn
     from svpc_amd.translator import Translator
@@ -479,42 +488,43 @@ def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup, dump_
     # GEMVs) against HBM.  Algorithmic work per SURVEY §8(d): encoder side 5.9e10·(L/6) FLOP per video (the train forward's clip
     # encoder + step encoder + simulator), an iteration reads every decoder / head / pointer weight once (fp32 master weights).
     roof = None
-    try:
-        from svpc_amd import ops as _ops
-        tr_e = Translator(type("O", (), {"cuda": True})(), {"model_cfg": cfg, "model": model.state_dict()}, model=model,
-                          incremental=not args.decode_full, graph=False)
-        tr_e.translate_batch(syn.translate_inputs(b))
-        tr_e.phase_events = []
-        tr_e.translate_batch(syn.translate_inputs(b))
-        torch.cuda.synchronize()
-        e = tr_e.phase_events
-        enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
-        D_, L_, V_, F_, Lv_, Lt_ = cfg.hidden_size, cfg.num_hidden_layers, cfg.vocab_size, cfg.video_feature_size, cfg.max_v_len, cfg.max_t_len
-        rows = n_vid * args.clips * Lv_
-        enc_flop = 2.0 * rows * F_ * D_ + L_ * rows * (8.0 * D_ * D_ + 4.0 * D_ * cfg.intermediate_size + 4.0 * Lv_ * D_)
-        terms = MFMA_TERMS[_ops.get_precision()]
-        w_iter = (L_ * 5 * D_ * D_ + 2 * D_ * D_ + D_ * V_ + D_ * D_) * 4.0          # decoder layers (QKV, cross-Q, out) + head + Wing, fp32
-        # (frac = the ALGORITHMIC product's FLOP over the peak, as the headline's roofline.frac; the three-term mode ISSUES `terms` × that
-        # MFMA work: achieved_issued / frac_issued)
-        roof = {"encoder_side": {"ms": enc_ms, "bound": "mfma", "algorithmic_flop": enc_flop, "mfma_terms_per_product": terms,
-                                 "achieved": enc_flop / (enc_ms * 1e-3) / 1e12, "peak": MFMA_PEAK_TFLOPS[_ops.get_precision()],
-                                 "unit": "TFLOP/s", "frac": enc_flop / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[_ops.get_precision()],
-                                 "achieved_issued": enc_flop * terms / (enc_ms * 1e-3) / 1e12,
-                                 "frac_issued": enc_flop * terms / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[_ops.get_precision()]},
-                "decoding_iterations": {"ms": dec_ms, "iterations": Lt_, "ms_per_iteration": dec_ms / Lt_, "bound": "hbm",
-                                        "algorithmic_bytes_per_iteration": w_iter,
-                                        "achieved": w_iter / (dec_ms / Lt_ * 1e-3) / 1e9, "peak": HBM_PEAK_TBPS * 1e3, "unit": "GB/s",
-                                        "frac": w_iter / (dec_ms / Lt_ * 1e-3) / 1e12 / HBM_PEAK_TBPS,
-                                        "note": "%d sentences advance one token per iteration through a chain of ~60 dependent launches "
-                                                "of 5-15 us each: the iterations are launch-latency-bound, not byte-bound" % (n_vid * args.clips)},
-                "measured": "one eager call bracketed with HIP events on the launch stream (eager launch overhead included: an upper "
-                            "bound on the replayed graph's phase times; eager total %.2f ms vs replayed %.2f ms)"
-                            % (enc_ms + dec_ms, 1000.0 * elapsed / steps)}
-    except Exception as ex:  # noqa: BLE001
-        roof = {"error": "%s: %s" % (type(ex).__name__, str(ex)[:200])}
+    if roofline:
+        try:
+            from svpc_amd import ops as _ops
+            tr_e = Translator(type("O", (), {"cuda": True})(), {"model_cfg": cfg, "model": model.state_dict()}, model=model,
+                              incremental=not args.decode_full, graph=False)
+            tr_e.translate_batch(syn.translate_inputs(b))
+            tr_e.phase_events = []
+            tr_e.translate_batch(syn.translate_inputs(b))
+            torch.cuda.synchronize()
+            e = tr_e.phase_events
+            enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+            D_, L_, V_, F_, Lv_, Lt_ = cfg.hidden_size, cfg.num_hidden_layers, cfg.vocab_size, cfg.video_feature_size, cfg.max_v_len, cfg.max_t_len
+            rows = n_vid * args.clips * Lv_
+            enc_flop = 2.0 * rows * F_ * D_ + L_ * rows * (8.0 * D_ * D_ + 4.0 * D_ * cfg.intermediate_size + 4.0 * Lv_ * D_)
+            terms = MFMA_TERMS[_ops.get_precision()]
+            w_iter = (L_ * 5 * D_ * D_ + 2 * D_ * D_ + D_ * V_ + D_ * D_) * 4.0          # decoder layers (QKV, cross-Q, out) + head + Wing, fp32
+            # (frac = the ALGORITHMIC product's FLOP over the peak, as the headline's roofline.frac; the three-term mode ISSUES `terms` × that
+            # MFMA work: achieved_issued / frac_issued)
+            roof = {"encoder_side": {"ms": enc_ms, "bound": "mfma", "algorithmic_flop": enc_flop, "mfma_terms_per_product": terms,
+                                     "achieved": enc_flop / (enc_ms * 1e-3) / 1e12, "peak": MFMA_PEAK_TFLOPS[_ops.get_precision()],
+                                     "unit": "TFLOP/s", "frac": enc_flop / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[_ops.get_precision()],
+                                     "achieved_issued": enc_flop * terms / (enc_ms * 1e-3) / 1e12,
+                                     "frac_issued": enc_flop * terms / (enc_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[_ops.get_precision()]},
+                    "decoding_iterations": {"ms": dec_ms, "iterations": Lt_, "ms_per_iteration": dec_ms / Lt_, "bound": "hbm",
+                                            "algorithmic_bytes_per_iteration": w_iter,
+                                            "achieved": w_iter / (dec_ms / Lt_ * 1e-3) / 1e9, "peak": HBM_PEAK_TBPS * 1e3, "unit": "GB/s",
+                                            "frac": w_iter / (dec_ms / Lt_ * 1e-3) / 1e12 / HBM_PEAK_TBPS,
+                                            "note": "%d sentences advance one token per iteration through a chain of ~60 dependent launches "
+                                                    "of 5-15 us each: the iterations are launch-latency-bound, not byte-bound" % (n_vid * args.clips)},
+                    "measured": "one eager call bracketed with HIP events on the launch stream (eager launch overhead included: an upper "
+                                "bound on the replayed graph's phase times; eager total %.2f ms vs replayed %.2f ms)"
+                                % (enc_ms + dec_ms, 1000.0 * elapsed / steps)}
+        except Exception as ex:  # noqa: BLE001
+            roof = {"error": "%s: %s" % (type(ex).__name__, str(ex)[:200])}
     from svpc_amd import ops as _ops2
     prec = _ops2.get_precision()
-    return {"metric": "greedy-decode captions/sec (vivt, 64 videos)", "value": caps / elapsed, "unit": "captions/s",
+    line = {"metric": "greedy-decode captions/sec (vivt, 64 videos)", "value": caps / elapsed, "unit": "captions/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1000.0 * elapsed / steps,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": prec, "mode": prec, "parity": recorded_config5(prec), "roofline": roof, "data": "synthetic",
@@ -527,6 +537,9 @@ def run_decode(cfg, model, args, device, world, rank, dist, steps, warmup, dump_
                                  ("hipGraph replay per batch structure (inputs copied into the captured buffers)" +
                                   ("; the two halves of the batch as two graphs on two streams (the launch-bound decoding iterations of one "
                                    "half beside the other's)" if (getattr(tr, "two_streams", False) and n_vid >= 2 * getattr(tr, "min_half", 8)) else ""))}}
+    if not roofline:
+        del line["roofline"]
+    return line
 
 
 def ragged_batches(cfg, args, device, n_structs, seed=4242, shared_features=False):
@@ -571,8 +584,9 @@ def ragged_batches(cfg, args, device, n_structs, seed=4242, shared_features=Fals
     return out, clips
 
 
-def run_train(args, precision, device, world, rank, dist, steps, warmup, instrument=True, ragged=0, dump_dir=None):
-    """Build model + optimizer in ``precision``, warm up, capture, time ``steps`` steps.  → dict (rank-0 view)."""
+def run_train(args, precision, device, world, rank, dist, steps, warmup, instrument=True, ragged=0, dump_dir=None, full=False):
+    """Build model + optimizer in ``precision``, warm up, capture, time ``steps`` steps.  → dict (rank-0 view).  Legs that take steps
+    of their own after the timed region (the replayed step's roofline, the exposed exchange time) run only with ``full``."""
     import torch
     from svpc_amd import ops, synthetic as syn
     from svpc_amd.graph import GraphedTrainStep, backward_all
@@ -649,6 +663,8 @@ def run_train(args, precision, device, world, rank, dist, steps, warmup, instrum
 
     def attn_timer():
         return {"select": lambda n_pairs, mq, mk: n_pairs == n_pairs_enc and mq == cfg.max_v_len and mk == cfg.max_v_len, "fwd": [], "bwd": []}
+    # eager steps are bracketed inside the timed region at no extra step; a replayed step needs instrumented eager steps of its own
+    instrument = instrument and (graph is None or full)
     if graph is None and instrument:
         ops.GEMM_TIMER = ops.KernelTimer(select=dom_select)
         ops.ATTN_TIMER = attn_timer()
@@ -672,7 +688,7 @@ def run_train(args, precision, device, world, rank, dist, steps, warmup, instrum
     # exposed exchange time: the same steps with the all-reduce calls skipped (gradients stay local — timing only, after the
     # timed region); difference of the two = what the exchange adds to a step after overlap
     no_exchange_ms = None
-    if exchange_on and reducer is not None and world > 1:
+    if full and exchange_on and reducer is not None and world > 1:
         reducer.skip = True
         for _ in range(2):
             step()
@@ -893,7 +909,7 @@ def worker(args):
             ops.set_precision(args.precision)
             cfg, model = build(args, device)
             out = run_decode(cfg, model, args, device, world, rank, dist if world > 1 else None, args.steps, args.warmup,
-                             dump_dir=args.dump_outputs)
+                             dump_dir=args.dump_outputs, roofline=args.full)
             if rank == 0:
                 print(json.dumps(out))
         else:
@@ -902,15 +918,55 @@ def worker(args):
         dist.destroy_process_group()
 
 
+def train_roofline(args, r):
+    """the headline's ``roofline`` object: the dominant kernel's launches (and the clip-encoder attention's) bracketed by run_train"""
+    precision, cfg, gsum = args.precision, r["cfg"], r["gsum"]
+    terms = MFMA_TERMS[precision]
+    achieved = terms * gsum["work"] / (gsum["ms"] * 1e-3) / 1e12 if gsum["ms"] > 0 else 0.0
+    D_, F_, L_ = cfg.hidden_size, cfg.video_feature_size, cfg.num_hidden_layers
+    n_l = max(1, gsum["launches"])
+    alg_bytes, alg_flop = gsum["bytes"] / n_l, gsum["work"] / n_l
+    default_cfg = (args.batch, args.clips, L_, D_, F_, args.model_type) == (16, 12, 6, 768, 3072, "vivt") and r["bf16_stream"]
+    traffic, traffic_src = measured_traffic(precision) if (default_cfg and r["glds"]) else (None, None)
+    if precision == "bf16x3" and r["bf16_stream"]:
+        kname = ("gemm_p8x3_kernel (split-bf16 three-term product A_lo·B_hi + A_hi·B_hi + A_hi·B_lo on the bf16 matrix cores; operands and "
+                 "output stored as two bf16 planes; 256x256 tiles, a staged buffer = hi and lo plane of one 32-deep k-slice of both operands "
+                 "(24 MFMAs per 12 fragment reads), 8 phases per pair of buffers, both operands direct-to-LDS, v_mfma_f32_16x16x32_bf16)")
+    elif r["glds"]:
+        kname = ("gemm_p8_kernel (bf16·bf16→bf16, both operands direct-to-LDS, 256x256x64 tiles, 8 phases per pair of k-tiles, "
+                 "v_mfma_f32_16x16x32_bf16)")
+    else:
+        kname = "gemm_bf16_kernel<128,128,NT,interior,8 waves,%s>" % ("bf16·f32→bf16" if r["bf16_stream"] else "f32")
+    return {"bound": "mfma", "kernel": "%s — every forward projection of the clip-encoder activation stream (M=%d rows: "
+                      "Q/K/V, attention-out, FFN, video embedding)" % (kname, r["rows_enc"]),
+            # `achieved` / `frac`: SURVEY §8(d)'s algorithmic work (2·M·N·K per launch) ÷ the measured launch time — the roofline
+            # fraction of the PRODUCT.  The three-term mode issues `mfma_terms_per_product` bf16 MFMA products per algorithmic
+            # one: `achieved_issued` / `frac_issued` say how busy the matrix pipe is (its utilisation), not useful throughput.
+            "achieved": achieved / terms, "peak": MFMA_PEAK_TFLOPS[precision], "unit": "TFLOP/s",
+            "frac": achieved / terms / MFMA_PEAK_TFLOPS[precision],
+            "achieved_issued": achieved, "frac_issued": achieved / MFMA_PEAK_TFLOPS[precision],
+            "traffic": traffic, "traffic_source": traffic_src,
+            "mfma_terms_per_product": terms,
+            "algorithmic_flop_per_launch": alg_flop, "issued_mfma_flop_per_launch": alg_flop * terms,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "launches": gsum["launches"], "avg_launch_ms": gsum["ms"] / max(1, gsum["launches"]),
+            "event_pair_overhead_ms": gsum["event_overhead_ms"],
+            "measured": "HIP events on the launch stream (net of the calibrated empty event-pair time), " +
+                        ("3 instrumented EAGER steps right after the timed graph replays (events cannot be recorded inside a replay; "
+                         "rocprofv3's average over the replays is kept in profiles/ as the cross-check)"
+                         if r["launch"].startswith("hipGraph") else "inside the timed region"),
+            "attention": r["asum"]}
+
+
 def _train_main(args, device, world, rank, dist, joined):
     import torch
     from svpc_amd import ops
     r = run_train(args, args.precision, device, world, rank, dist, args.steps, args.warmup,
-                  ragged=(args.ragged if (world == 1 and not args.rehearse_dp and not args.no_secondary) else 0),
-                  dump_dir=args.dump_outputs)
+                  ragged=(args.ragged if (args.full and world == 1 and not args.rehearse_dp and not args.no_secondary) else 0),
+                  dump_dir=args.dump_outputs, full=args.full)
     cfg, gsum = r["cfg"], r["gsum"]
     extras = {}
-    if world == 1 and not args.no_secondary and not args.rehearse_dp:
+    if args.full and world == 1 and not args.no_secondary and not args.rehearse_dp:
         # N=1-only legs, all after the timed region: config 5 (greedy decode, in the headline mode), the two other arithmetic modes
         # on the same workload, and the two same-box ceilings (vendor GEMM, copy bandwidth)
         try:
@@ -966,22 +1022,6 @@ def _train_main(args, device, world, rank, dist, joined):
         return
     ms, elapsed = r["ms"], r["elapsed"]
     precision = args.precision
-    terms = MFMA_TERMS[precision]
-    achieved = terms * gsum["work"] / (gsum["ms"] * 1e-3) / 1e12 if gsum["ms"] > 0 else 0.0
-    D_, F_, L_ = cfg.hidden_size, cfg.video_feature_size, cfg.num_hidden_layers
-    n_l = max(1, gsum["launches"])
-    alg_bytes, alg_flop = gsum["bytes"] / n_l, gsum["work"] / n_l
-    default_cfg = (args.batch, args.clips, L_, D_, F_, args.model_type) == (16, 12, 6, 768, 3072, "vivt") and r["bf16_stream"]
-    traffic, traffic_src = measured_traffic(precision) if (default_cfg and r["glds"]) else (None, None)
-    if precision == "bf16x3" and r["bf16_stream"]:
-        kname = ("gemm_p8x3_kernel (split-bf16 three-term product A_lo·B_hi + A_hi·B_hi + A_hi·B_lo on the bf16 matrix cores; operands and "
-                 "output stored as two bf16 planes; 256x256 tiles, a staged buffer = hi and lo plane of one 32-deep k-slice of both operands "
-                 "(24 MFMAs per 12 fragment reads), 8 phases per pair of buffers, both operands direct-to-LDS, v_mfma_f32_16x16x32_bf16)")
-    elif r["glds"]:
-        kname = ("gemm_p8_kernel (bf16·bf16→bf16, both operands direct-to-LDS, 256x256x64 tiles, 8 phases per pair of k-tiles, "
-                 "v_mfma_f32_16x16x32_bf16)")
-    else:
-        kname = "gemm_bf16_kernel<128,128,NT,interior,8 waves,%s>" % ("bf16·f32→bf16" if r["bf16_stream"] else "f32")
     dtype = {"bf16": "bf16", "fp32": "f32", "bf16x3": "bf16x3"}[precision]
     arithmetic = {"bf16": "bf16 MFMA operands (one-term products), fp32 accumulate, bf16 activation streams; statistics, losses, master "
                           "weights, optimizer fp32",
@@ -1003,26 +1043,9 @@ def _train_main(args, device, world, rank, dist, joined):
                    "host_enqueue_ms_per_step": r["host_enqueue_ms"], "launch": r["launch"], "degraded": r["degraded"],
                    "text_rows": r["text_rows"],
                    "gpus_requested": args.gpus},
-        "roofline": {"bound": "mfma", "kernel": "%s — every forward projection of the clip-encoder activation stream (M=%d rows: "
-                               "Q/K/V, attention-out, FFN, video embedding)" % (kname, r["rows_enc"]),
-                     # `achieved` / `frac`: SURVEY §8(d)'s algorithmic work (2·M·N·K per launch) ÷ the measured launch time — the roofline
-                     # fraction of the PRODUCT.  The three-term mode issues `mfma_terms_per_product` bf16 MFMA products per algorithmic
-                     # one: `achieved_issued` / `frac_issued` say how busy the matrix pipe is (its utilisation), not useful throughput.
-                     "achieved": achieved / terms, "peak": MFMA_PEAK_TFLOPS[precision], "unit": "TFLOP/s",
-                     "frac": achieved / terms / MFMA_PEAK_TFLOPS[precision],
-                     "achieved_issued": achieved, "frac_issued": achieved / MFMA_PEAK_TFLOPS[precision],
-                     "traffic": traffic, "traffic_source": traffic_src,
-                     "mfma_terms_per_product": terms,
-                     "algorithmic_flop_per_launch": alg_flop, "issued_mfma_flop_per_launch": alg_flop * terms,
-                     "algorithmic_bytes_per_launch": alg_bytes,
-                     "launches": gsum["launches"], "avg_launch_ms": gsum["ms"] / max(1, gsum["launches"]),
-                     "event_pair_overhead_ms": gsum["event_overhead_ms"],
-                     "measured": "HIP events on the launch stream (net of the calibrated empty event-pair time), " +
-                                 ("3 instrumented EAGER steps right after the timed graph replays (events cannot be recorded inside a replay; "
-                                  "rocprofv3's average over the replays is kept in profiles/ as the cross-check)"
-                                  if r["launch"].startswith("hipGraph") else "inside the timed region"),
-                     "attention": r["asum"]},
     }
+    if gsum is not None:
+        out["roofline"] = train_roofline(args, r)
     if dist is not None:
         out["rccl_ranks"] = joined
         out["distinct_devices"] = min(joined, torch.cuda.device_count())      # < n_gpus only in a gloo rehearsal that shares cards
@@ -1051,7 +1074,7 @@ def _train_main(args, device, world, rank, dist, joined):
                     rg["cold"]["vs_padded_uniform_steps_per_s"] = rg["cold"]["steps_per_s"] / pad["steps_per_s"]
         out["ragged"] = rg
     out.update(extras)
-    if world == 1 and not args.no_cpu_baseline and not args.rehearse_dp:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.rehearse_dp:
         out["cpu_baseline"] = cpu_baseline(cfg, r["model"], args)
         physical, logical, usable = host_cpus()
         if args.cpu_alt and args.cpu_threads <= 0 and physical > out["cpu_baseline"]["cores"]:

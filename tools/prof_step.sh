@@ -6,7 +6,7 @@ root="$(pwd)"
 out="$root/gpurun_out/$name"
 mkdir -p "$out"
 export TMPDIR=/tmp
-cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o p -- python3 "$root/bench.py" "$@" > "$out/bench.log" 2>&1
+cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o p -- python3 "$root/bench.py" --full "$@" > "$out/bench.log" 2>&1
 rc=$?
 cd "$root"
 trace=$(find "$out" -name "p_kernel_trace.csv" | head -1)
