@@ -514,6 +514,21 @@ int svpc_beam_step_ctl(const float* scores, int ld, const int* row_c, const int*
  * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */
 int svpc_beam_finalize_nbest(const float* cum, const int* len, const double* lp, const int* ext, int ld_tok, int n_sent, int beam, int lt,
                              int n_best, int* best_ids, float* best_score, int* best_len, svpc_stream_t stream);
+/* random-sampling decoding step (the random-sampling strategy of the reference's OpenNMT decode-strategy lineage: random_sampling_temp,
+ * random_sampling_topk, random_sampling_topp): one wave per sample row r of `scores` (n_rows rows; row r: its first row_c[r] <= max_c <= 4096
+ * columns, the last row_x[r] of them copied OOV words).  Step scores as svpc_beam_step's (logits == 0: log p; logits != 0: logit − the
+ * log-sum-exp of the row without unk).  Candidates: columns != unk with a finite step score, eos excluded while pos + 1 <= min_len, in order
+ * of higher raw value then lower column; top-k (topk > 0) keeps the first topk, z = (double)step / temp, top-p (0 < topp < 1) keeps the
+ * shortest prefix holding topp of the mass exp(z − z_first); the pick is the Gumbel-max over what is kept, with u = (svpc_hash32(*seed, pos,
+ * r·4096 + c) + 0.5)·2^-32, ties to the lower column.  In place: cum (fp32 cum + step), finished (pick eos), len (pos + 1); a finished row
+ * takes pad (step 0, len kept), a row without candidates pad, cum −inf, finished.  Out: next_ext / next_model (OOV → unk on the model side)
+ * and column pos + 1 of the (n_rows, ld_tok) id matrices text_out / ext_out.  *seed is read on the device: graph-capture safe. */
+int svpc_sample_step(const float* scores, int ld, const int* row_c, const int* row_x, int n_rows, int max_c, int pos, int logits, int unk,
+                     int eos, int pad, double temp, int topk, double topp, int min_len, const long long* seed, float* cum, int* finished,
+                     int* len, int* text_out, int* ext_out, int ld_tok, int* next_ext, int* next_model, svpc_stream_t stream);
+/* the seed of one sampling decode, on the device: src = (fixed, value); fixed != 0: *used = value; otherwise *used is drawn from the
+ * decode's seed word *word, which advances (consecutive replays of one captured decode draw different streams) */
+int svpc_sample_seed(const long long* src, long long* word, long long* used, svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

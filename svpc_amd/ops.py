@@ -2684,3 +2684,95 @@ def beam_finalize_nbest(cum, ext, beam, n_best, length=None, lp=None):
     _lib.call("beam_finalize_nbest", _p(cum), _p(length), _p(lp), _p(ext), lt, T, int(beam), lt, int(n_best), _p(ids), _p(score), _p(ln),
               _stream())
     return ids, score, ln
+
+
+SAMPLE_COLS_MAX = 4096          # columns of a sample row (the draw index is r·4096 + c)
+
+
+def check_sampling(lt, num_samples=1, random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0,
+                   seed=None, max_cols=None):
+    """The settings of a random-sampling decode over Lt = ``lt`` positions, checked on the host (ValueError) and normalised → dict(
+    num_samples R (1 … BEAM_MAX), random_sampling_temp τ (finite > 0), random_sampling_topk k (0: off; OpenNMT's −1 is taken as 0),
+    random_sampling_topp q (in [0, 1]; 0 and 1: off), min_length m (0 … Lt − 1), seed (None or an int in [0, 2⁶³))).  ``max_cols``: the
+    widest score row C_r = V + X of the batch (≤ SAMPLE_COLS_MAX)."""
+    def as_int(name, v):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        return int(v)
+    R = as_int("num_samples", num_samples)
+    if not 1 <= R <= BEAM_MAX:
+        raise ValueError("num_samples must be 1..%d, got %d" % (BEAM_MAX, R))
+    try:
+        temp = float(random_sampling_temp)
+    except (TypeError, ValueError):
+        raise ValueError("random_sampling_temp must be a number, got %r" % (random_sampling_temp,))
+    if not math.isfinite(temp) or temp <= 0:
+        raise ValueError("random_sampling_temp must be finite and > 0, got %r" % (random_sampling_temp,))
+    k = as_int("random_sampling_topk", random_sampling_topk)
+    if k < -1:
+        raise ValueError("random_sampling_topk must be >= -1 (0 or -1: the full distribution), got %d" % k)
+    try:
+        q = float(random_sampling_topp)
+    except (TypeError, ValueError):
+        raise ValueError("random_sampling_topp must be a number, got %r" % (random_sampling_topp,))
+    if not 0.0 <= q <= 1.0:                       # (NaN fails too)
+        raise ValueError("random_sampling_topp must be in [0, 1], got %r" % (random_sampling_topp,))
+    m = as_int("min_length", min_length)
+    if not 0 <= m <= lt - 1:
+        raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (lt - 1, m))
+    if seed is not None:
+        seed = as_int("seed", seed)
+        if not 0 <= seed < 1 << 63:
+            raise ValueError("seed must be None or an integer in [0, 2**63), got %d" % seed)
+    if max_cols is not None and int(max_cols) > SAMPLE_COLS_MAX:
+        raise ValueError("sampling reads score rows of at most %d columns (vocabulary + copied words), got %d" % (SAMPLE_COLS_MAX, max_cols))
+    return dict(num_samples=R, random_sampling_temp=temp, random_sampling_topk=max(k, 0), random_sampling_topp=q, min_length=m, seed=seed)
+
+
+def sample_step(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished, length, text, ext, seed, *, temp=1.0, topk=0, topp=0.0,
+                min_length=0, max_cols=None):
+    """One random-sampling step (svpc_sample_step) over ``scores`` (T·R, ≥ C) — probabilities, or logits when ``logits``: every row draws
+    its pick at position pos + 1 from its step scores / ``temp`` restricted to the top-``topk`` columns and the top-``topp`` mass (0: off),
+    EOS barred while pos + 1 ≤ ``min_length``.  ``seed`` is a device int64 (1,) tensor (read by the kernel: a captured graph replays with
+    whatever it holds).  ``cum`` fp32, ``finished`` / ``length`` int32 (T·R,) are updated in place, and column pos + 1 of the (T·R, Lt)
+    int32 id matrices ``text`` / ``ext``.  ``max_cols``: max(row_c) when the caller knows it (else taken from the host copy).
+    → (next_ext, next_model) int32 (T·R,)."""
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("sample_step: scores must be fp32 (T·R, C) rows with unit column stride")
+    for t, dt in ((cum, torch.float32), (finished, torch.int32), (length, torch.int32)):
+        if t.dtype != dt or t.shape != (R,) or not t.is_contiguous() or t.device != scores.device:
+            raise ValueError("sample_step: cum fp32, finished and length int32, all contiguous (T·R,) on the scores' device")
+    lt = text.shape[1]
+    for m in (text, ext):
+        if m.dtype != torch.int32 or not m.is_contiguous() or tuple(m.shape) != (R, lt) or m.device != scores.device:
+            raise ValueError("sample_step: id matrices must be contiguous int32 (T·R, Lt) on the scores' device")
+    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
+        raise ValueError("sample_step: seed must be a device int64 tensor")
+    if not 0 <= pos < lt - 1:
+        raise ValueError("sample_step: position %d outside the %d-column matrices" % (pos, lt))
+    if not (math.isfinite(temp) and temp > 0 and topk >= 0 and 0.0 <= topp <= 1.0 and 0 <= min_length < lt):
+        raise ValueError("sample_step: temp finite > 0, topk >= 0, topp in [0, 1], min_length 0..Lt-1")
+    rc = as_idx(row_c)
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > SAMPLE_COLS_MAX or max_c > scores.shape[1]:
+        raise ValueError("sample_step: rows of at most %d columns, inside the score matrix" % SAMPLE_COLS_MAX)
+    _need_gpu(scores)
+    dev = scores.device
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("sample_step", _p(scores), scores.stride(0), _p(rc.dev(dev)), _p(as_idx(row_x).dev(dev)), R, int(max_c), int(pos),
+              1 if logits else 0, int(unk), int(eos), int(pad), float(temp), int(topk), float(topp), int(min_length), _p(seed), _p(cum),
+              _p(finished), _p(length), _p(text), _p(ext), lt, _p(nxt_ext), _p(nxt), _stream())
+    return nxt_ext, nxt
+
+
+def sample_seed(src, word, used):
+    """The seed of one sampling decode, on the device (svpc_sample_seed): ``src`` int64 (2,) = (fixed, value); fixed: ``used`` = value,
+    otherwise ``used`` is drawn from the seed word ``word`` (int64 (1,)), which advances.  All three device tensors."""
+    for t, n in ((src, 2), (word, 1), (used, 1)):
+        if t.dtype != torch.int64 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("sample_seed: src int64 (2,), word and used int64 (1,), contiguous device tensors")
+    _need_gpu(src)
+    _lib.call("sample_seed", _p(src), _p(word), _p(used), _stream())
+    return used

@@ -54,6 +54,32 @@ default to off, and with every control off nothing changes (same ids, scores, la
 
 The per-layer KV caches hold one slot of Lt rows per hypothesis; a row is written once, into the slot of the hypothesis that computes it,
 and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that the attention reads through (no cache copy per step).
+
+**Random sampling** (the random-sampling half of the reference's OpenNMT decode-strategy lineage, which vendored only the beam half):
+``translate_batch_sample(model_inputs, num_samples=1, **kw)`` → ``(dec_seq_list, oov_word_dict, score_list, length_list)``: per video ids
+(S_b, R, Lt) int64 (extended ids, BOS at position 0, PAD after EOS), cum (S_b, R) fp32 and len (S_b, R) int64, samples in sample order
+(not sorted).  Keywords override ``opt`` attributes of the same name (``getattr`` defaults, as the decoding controls):
+``random_sampling_temp`` τ (1.0), ``random_sampling_topk`` k (0: the full distribution; OpenNMT's −1 is taken as 0),
+``random_sampling_topp`` q (0.0: off), ``min_length`` m (0); ``seed`` is keyword-only (the reference's ``opt.seed`` is its training seed).
+
+- sample j of sentence t is row r = t·R + j, 1 ≤ R ≤ 8; every sample starts alive at BOS; C_r = V + X columns (X = 0 in ``video``
+  mode); step i = 0 … Lt − 2 picks position p = i + 1;
+- one step of a live row: raw_c is the mixed probability (pointer modes) or the logit (``video``); the step score s_c is beam's (fp64,
+  rounded once: log raw_c, −inf for raw_c ≤ 0; or raw_c − the log-sum-exp of the row without UNK); candidates K0 are the columns c < C_r,
+  c ≠ UNK, s_c > −inf, and not EOS while p ≤ m, ordered by higher raw_c then lower c; top-k keeps the first min(k, |K0|) (K1); z_c =
+  (double)s_c / τ; top-p (0 < q < 1) keeps the shortest prefix K2 of K1 with Σ w ≥ q·W, w_c = exp(z_c − z_first), W = Σ_K1 w; the pick
+  is argmax over K2 of z_c + g_c, g_c = −log(−log u_c), u_c = (svpc_hash32(seed, i, r·4096 + c) + 0.5)·2⁻³² (Gumbel-max: an exact draw
+  from softmax(z) over K2), ties to the lower c;
+- the pick's extended id is kept, the model side sees UNK for a copied word; cum = fp32(cum + s_pick); len = p; EOS finishes the row; a
+  finished row takes PAD (step score 0, len kept); a row with an empty K0 takes PAD, cum −inf, finished, len p;
+- so k = 1, m = 0, R = 1 gives greedy's ids up to the first EOS (PAD after it) for any τ, q and seed, and k = 1 makes a sentence's R
+  samples identical;
+- ``seed=s`` (an int in [0, 2⁶³)) draws from the stream keyed by s alone: the same ids eagerly and replayed, whatever ran before;
+  ``seed=None`` draws a fresh stream each call from a device-resident seed word that the decode advances itself (consecutive replays of
+  one captured graph differ); ``last_sample_seed`` (a device int64 (1,) tensor) holds the seed the last call used;
+- every argument is checked on the host before any device work: ValueError for R, τ (finite > 0), k (≥ −1), q ([0, 1]), m (0 … Lt − 1),
+  the seed, and rows wider than 4096 columns; TypeError for an unknown keyword; ``incremental=False`` raises NotImplementedError.
+  Each setting (R, τ, k, q, m) has its own prepared plan and captured graph; the seed is a captured input.
 """
 from __future__ import annotations
 
@@ -61,7 +87,7 @@ import torch
 
 from . import ops
 from .model import BatchPlan, _Ctx
-from .ops import check_beam_controls, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
+from .ops import check_beam_controls, check_sampling, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
 from .ops_common import ACT_RELU, Idx, SeqInfo
 from .synthetic import BOS, EOS, PAD, UNK
 
@@ -80,6 +106,8 @@ class Translator(object):
         self.phase_events = None    # bench.py: a list → _decode_core (eager) appends three HIP events: start, encoder side done, end
         self._preps = {}
         self._ttab = None
+        self._seed_word = None      # sampling with seed=None: the device-resident seed word the decode advances (see translate_batch_sample)
+        self.last_sample_seed = None
         self.device = torch.device("cuda" if getattr(opt, "cuda", True) else "cpu")
         self.model_config = checkpoint["model_cfg"]
         self.max_t_len = self.model_config.max_t_len
@@ -162,6 +190,26 @@ class Translator(object):
         ctl, key = self._controls(controls, beam=B, n_best=n_best if n_best is not None else getattr(self.opt, "n_best", 1))
         return self._translate_beam(model_inputs, B, ctl, key, ctl["n_best"])
 
+    SAMPLING = dict(random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0)
+
+    @torch.no_grad()
+    def translate_batch_sample(self, model_inputs, num_samples=1, seed=None, **kw):
+        """``num_samples`` random samples per sentence (module docstring) → (dec_seq_list, oov_word_dict, score_list, length_list): per
+        video ids (S_b, R, Lt) int64, cum (S_b, R) fp32 and len (S_b, R) int64, in sample order."""
+        unknown = set(kw) - set(self.SAMPLING)
+        if unknown:
+            raise TypeError("unknown sampling keyword(s): %s" % ", ".join(sorted(unknown)))
+        val = {k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.SAMPLING.items()}
+        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
+         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
+        n_oov = [len(d) for d in oov_word_dict] if self.model_config.model_mode != "video" else [0]
+        s = check_sampling(self.max_t_len, num_samples=num_samples, seed=seed, max_cols=self.model_config.vocab_size + max(n_oov + [0]), **val)
+        if not self.incremental:
+            raise NotImplementedError("sampling decodes incrementally only (Translator(incremental=True))")
+        key = ("sample", s["num_samples"], s["random_sampling_temp"], s["random_sampling_topk"], s["random_sampling_topp"], s["min_length"])
+        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
+                               ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=s["num_samples"], sample=(key, s["seed"]))
+
     def _translate_beam(self, model_inputs, B, ctl, key, n_best):
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
          ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
@@ -170,7 +218,8 @@ class Translator(object):
                                n_best=n_best)
 
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
-    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0, ctl=None, ranked=False):
+    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0, ctl=None, ranked=False,
+                 sample=None):
         cfg = model.config
         mode = cfg.model_mode
         Lt, V = cfg.max_t_len, cfg.vocab_size
@@ -179,7 +228,7 @@ class Translator(object):
         n_oov = [len(d) if mode != "video" else 0 for d in oov_word_dict]
         key = (tuple(int(v) for v in batch_step_num), sep_t.numpy().tobytes(), tuple(n_oov), S_pad, N, L, str(dev), self.incremental,
                tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts), beam,
-               ctl[1] if ctl is not None else None, ranked)
+               ctl[1] if ctl is not None else None, ranked, sample)
         prep = self._preps.get(key)
         if prep is not None:
             return prep
@@ -206,6 +255,15 @@ class Translator(object):
                     exclusion=(exclusion_bitmap(c["exclusion_tokens"], V, dev), V) if n and c["exclusion_tokens"] else None,
                     lp=(torch.tensor(length_penalty_table(c["length_penalty_name"], c["length_penalty_alpha"], Lt), dtype=torch.float64,
                                      device=dev) if c["length_penalty_name"] != "none" else None))
+            if sample is not None:
+                # sampling: every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed
+                # source (fixed, value) and the seed the decode used are captured device words
+                _, R, temp, topk, topp, m = sample
+                TR = T * R
+                prep.update(sample=dict(temp=temp, topk=topk, topp=topp, min_length=m), c_max=prep["plb"]["c_max"],
+                            key_rows=(torch.arange(TR, dtype=torch.int32, device=dev).unsqueeze(1) * Lt +
+                                      torch.arange(Lt, dtype=torch.int32, device=dev)).contiguous(),
+                            seed_src=torch.zeros(2, dtype=torch.int64, device=dev), seed_used=torch.zeros(1, dtype=torch.int64, device=dev))
         if len(self._preps) > 32:
             self._preps.clear()
         self._preps[key] = prep
@@ -322,7 +380,9 @@ class Translator(object):
 
     def _beam_iterations(self, model, prep, mem, bank, cx, tab):
         """The Lt − 1 selection steps of a beam decode over the T·B hypothesis rows → (ids (T, Lt) int32, score (T,) fp32); with controls
-        or n-best (``prep["ranked"]``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order."""
+        or n-best (``prep["ranked"]``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order.  Sampling
+        (``prep["sample"]``): the same iterations over the T·R sample rows, every row its own ancestry, ``ops.sample_step`` in place of the
+        selection → (ids (T·R, Lt) int32, cum (T·R,) fp32, len (T·R,) int32)."""
         cfg = model.config
         mode = cfg.model_mode
         B, T = prep["beam"], prep["T"]
@@ -343,39 +403,62 @@ class Translator(object):
         if seq_cross is None:          # (the fallback's segmentation: hypothesis r over the memory rows of its sentence r // B)
             seq_cross = prep["seq_cross"][key] = SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, dev)
         plb, row_xb = prep["plb"], prep["row_xb"]
-        # ping-pong (text ids, extended ids, KV-cache ancestry) tables: children are written from their parents' rows
-        toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
-        toks[0][0][:, 0] = BOS
-        toks[0][1][:, 0] = BOS
-        toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
-        cum = torch.zeros(T, B, dtype=torch.float32, device=dev)
-        cum[:, 1:] = float("-inf")                                                 # the first step: beam 0 alone
-        cum = cum.view(TB)
+        samp = prep.get("sample")
+        if samp is None:
+            # ping-pong (text ids, extended ids, KV-cache ancestry) tables: children are written from their parents' rows
+            toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
+            toks[0][0][:, 0] = BOS
+            toks[0][1][:, 0] = BOS
+            toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
+            cum = torch.zeros(T, B, dtype=torch.float32, device=dev)
+            cum[:, 1:] = float("-inf")                                             # the first step: beam 0 alone
+            cum = cum.view(TB)
+        else:
+            # sampling: one (text ids, extended ids) pair written in place; every sample starts alive at BOS
+            text = torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev)
+            text[:, 0] = BOS
+            ext = text.clone()
+            cum = torch.zeros(TB, dtype=torch.float32, device=dev)
+            ops.sample_seed(prep["seed_src"], self._seed_word_on(dev), prep["seed_used"])
         fin = torch.zeros(TB, dtype=torch.int32, device=dev)
         nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
         ranked = prep["ranked"]                   # decoding controls and / or n-best: lengths tracked, the finals sorted by their key
         ctl = prep.get("ctl")
-        length = torch.zeros(TB, dtype=torch.int32, device=dev) if ranked else None
+        length = torch.zeros(TB, dtype=torch.int32, device=dev) if ranked or samp is not None else None
         for i in range(Lt - 1):
-            t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
+            t_in, t_out = (toks[i % 2], toks[(i + 1) % 2]) if samp is None else (None, None)
+            rows = t_in[2] if samp is None else prep["key_rows"]
             seq_self = prep["seq_self_b"].get(i)
             if seq_self is None:
                 seq_self = prep["seq_self_b"][i] = SeqInfo.uniform(TB, 1, i + 1, dev)
             x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
             for layer, cache, kv in zip(layers, caches, mem_kv):
-                x = layer.step(x, i, Lt, cache, kv, seq_self, seq_cross, cx, key_rows=t_in[2], q_group=B)
+                x = layer.step(x, i, Lt, cache, kv, seq_self, seq_cross, cx, key_rows=rows, q_group=B)
             if mode == "video":
                 scores = model.decoder_classifier.run(x, cx.eps)          # raw logits: the step score is their log_softmax
             else:
                 scores, _ = model._lm_probs(x, bank, plb, cx, proj=proj)
-            if ranked:
+            if samp is not None:
+                _, nxt = ops.sample_step(scores, plb["row_c"], row_xb, i, mode == "video", UNK, EOS, PAD, cum, fin, length, text, ext,
+                                         prep["seed_used"], temp=samp["temp"], topk=samp["topk"], topp=samp["topp"],
+                                         min_length=samp["min_length"], max_cols=prep["c_max"])
+            elif ranked:
                 _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
                                           length=length, **ctl)
             else:
                 _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt)
+        if samp is not None:
+            return ext, cum, length
         if ranked:           # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
             return ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
         return ops.beam_finalize(cum, toks[(Lt - 1) % 2][1], B)
+
+    def _seed_word_on(self, dev):
+        """the sampling decodes' seed word (int64 (1,) on ``dev``): drawn once from torch's default generator, then advanced on the device
+        by every decode with seed=None; a captured graph holds its address"""
+        if self._seed_word is None or self._seed_word.device != torch.device(dev):
+            self._seed_word = torch.randint(0, 1 << 62, (1,), dtype=torch.int64).to(dev)
+        return self._seed_word
 
     @torch.no_grad()
     def translate_batch_greedy(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list,
@@ -385,10 +468,14 @@ class Translator(object):
                                ingr_id_dict, oov_word_dict, batch_step_num, rt_model)
 
     def _translate(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
-                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0, ctl=None, n_best=0):
+                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0, ctl=None, n_best=0, sample=None):
         model = rt_model
         dev = video_features_list[0].device
         ranked = bool(beam) and (n_best > 0 or (ctl is not None and ctl[1] is not None))
+        if sample is not None:
+            sample, seed = sample
+            if dev.type != "cuda":
+                raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
         # tensors are consecutive slices of one buffer (the usual collate output; model._stacked sees it) that is three launches on the
         # stacked views instead of three per step
@@ -412,13 +499,17 @@ class Translator(object):
         def part(lo, hi, stream=None):
             n = hi - lo
             prep = self._prepare(model, list(batch_step_num[lo:hi]), sep_all[lo:hi], list(ingr_id_dict[lo:hi]), list(oov_word_dict[lo:hi]),
-                                 S_pad, n, L, dev, beam=beam, ctl=ctl, ranked=ranked)
+                                 S_pad, n, L, dev, beam=beam, ctl=ctl, ranked=ranked, sample=sample)
+            if sample is not None:       # the seed source of this call: a captured input, like the batch tensors
+                prep["seed_src"].copy_(torch.tensor([0, 0] if seed is None else [1, seed], dtype=torch.int64))
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
                 out = self._decode_core(model, prep, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
                                         src[2].reshape(-1).float(), src[3].reshape(-1))
             else:
                 out = self._decode_graphed(model, prep, src, (S_pad, n, L, F), stream)
+            if sample is not None:
+                self.last_sample_seed = prep["seed_used"].clone()
             return prep["plan"], out
 
         # Two halves on two streams: the encoder side of a batch is bound by the matrix cores, the Lt decoding
@@ -445,7 +536,11 @@ class Translator(object):
         res, scores, lens = [], [], []
         for plan, out in plans_outs:
             score = length = None
-            if ranked:
+            if sample is not None:
+                out, score, length = out
+                R = beam
+                out, score, length = out.view(-1, R, out.shape[1]), score.view(-1, R), length.view(-1, R).to(torch.int64)
+            elif ranked:
                 out, score, length = out
                 k = n_best or 1                        # (translate_batch_beam: row 0; translate_batch_nbest: the first n_best rows)
                 out, score, length = (out[:, :k], score[:, :k], length[:, :k].to(torch.int64)) if n_best else (out[:, 0], score[:, 0].contiguous(), None)
