@@ -509,6 +509,17 @@ int svpc_beam_step_ctl(const float* scores, int ld, const int* row_c, const int*
                        int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
                        int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
                        int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, svpc_stream_t stream);
+/* svpc_beam_step_ctl with paragraph-scope n-gram blocking (ngram n >= 1, ld_tok <= 64, rows of at most 4096 columns): candidate (h, w) is
+ * also skipped when the gram (ext_in[h][pos + 2 − n … pos], w) equals n consecutive words of an earlier sentence's caption and none of its
+ * ids is set in excl.  Those captions are rows of `hist` ((rows, ld_tok) int32 extended ids, the decode's top-1 matrix): sentence t of the
+ * step reads rows hist_desc[2t] … hist_desc[2t] + hist_desc[2t + 1] − 1.  The words of a row are its ids at positions 1 … L (position
+ * L + 1: its first eos or pad, else L = ld_tok − 1), bos excepted; no gram spans two rows.  With every history empty it is
+ * svpc_beam_step_ctl. */
+int svpc_beam_step_para(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                        int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                        int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
+                        int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, const int* hist, const int* hist_desc,
+                        int bos, svpc_stream_t stream);
 /* end of the beam decode, n-best: per sentence its n_best (1 … beam) hypotheses in order of (double)cum / lp[len] (lp NULL: cum), ties to
  * the lower beam index; their first lt ids of `ext` into best_ids ((n_sent, n_best, lt)), cum into best_score and len into best_len
  * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */

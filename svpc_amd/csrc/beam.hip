@@ -18,6 +18,13 @@
 // so a survivor's cum is today's.  A length penalty lp (a float64 table by length, null: none) ranks by key = (double)cum / lp[len], len
 // = p for a live parent's child and the stored length for a finished one: every child of one live row has the same len, so the key is
 // monotone in the raw value there and the per-row top-B by (raw, column) is unchanged; the B·B survivors rank by (key, raw, flat index).
+//
+// Paragraph scope (svpc_beam_step_para: the PARA instantiation, a separate kernel): n-gram blocking also bans candidate (h, w) when the gram
+// (y_{p-n+1} … y_pos, w) equals an n-gram of the words of an earlier sentence of the same video.  Those sentences' chosen captions are rows
+// of the decode's own top-1 extended-id matrix `hist`; sentence t reads rows hdesc[2t] … hdesc[2t] + hdesc[2t + 1] − 1.  The words of a
+// history row are its ids at positions 1 … L (L + 1: its first EOS or PAD, else ld_tok − 1), BOS not a word; a gram is n consecutive
+// positions that are all words, so none spans two sentences.  Each live row's bans (its own and the history's) are merged into an LDS
+// bitmap of kBanCols bits, read only by a column that would enter a lane's top-B.
 #include "common.h"
 
 #include <climits>
@@ -26,6 +33,8 @@ namespace {
 
 constexpr int kBeamMax = 8;
 constexpr int kBeamThreads = 256;
+constexpr int kBanCols = 4096;                     // paragraph scope: columns of a row's ban bitmap (ops.SAMPLE_COLS_MAX)
+constexpr int kBanWords = kBanCols / 32;
 
 __device__ __forceinline__ bool raw_better(float v, int c, float w, int d) { return v > w || (v == w && c < d); }
 
@@ -59,6 +68,7 @@ struct BeamArgs {
     int* text_out; int* ext_out; int* rows_out; int ld_tok;
     int* parent; int* next_ext; int* next_model;
     int min_len; int ngram; const unsigned* excl; int excl_v; const double* lp; int* len;    // controls (0 / null: off)
+    const int* hist; const int* hdesc; int bos;                                            // paragraph scope (PARA only)
 };
 
 // the top-B insertion of a row with banned words (ban[0 … nb), a short LDS list): the list is read only by a column that would enter
@@ -70,11 +80,19 @@ __device__ __forceinline__ void topb_insert_ban(float (&val)[B], int (&idx)[B], 
     topb_insert<B>(val, idx, v, c);
 }
 
+// the same with the banned words as a bitmap (paragraph scope)
+template <int B>
+__device__ __forceinline__ void topb_insert_bits(float (&val)[B], int (&idx)[B], float v, int c, const unsigned* bits) {
+    if (!raw_better(v, c, val[B - 1], idx[B - 1])) return;
+    if (c < kBanCols && ((bits[c >> 5] >> (c & 31)) & 1u)) return;
+    topb_insert<B>(val, idx, v, c);
+}
+
 __device__ __forceinline__ bool excluded(const BeamArgs& a, int y) {
     return a.excl != nullptr && y >= 0 && y < a.excl_v && ((a.excl[y >> 5] >> (y & 31)) & 1u);
 }
 
-template <int B>
+template <int B, bool PARA>
 __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
     constexpr int NC = B * B;                      // candidates that reach the final ranking (≤ 64: one lane each)
     __shared__ double c_key[NC];
@@ -83,7 +101,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
     __shared__ float p_cum[B];
     __shared__ int p_fin[B], p_len[B], n_cand;
     __shared__ int sel[B];
-    __shared__ int ban[B][64], n_ban[B];           // n-gram blocking: the banned words of every live row
+    __shared__ int ban[PARA ? 1 : B][64], n_ban[B];                         // n-gram blocking: the banned words of every live row
+    __shared__ unsigned ban_bits[PARA ? B : 1][PARA ? kBanWords : 1];      // … as a bitmap per row (paragraph scope)
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = t * B;
     const int pl = a.pos + 1;                     // position p of this step's pick
@@ -93,7 +112,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
     if (tid < NC) c_flat[tid] = INT_MAX;
     if (a.ngram == 0 || pl < a.ngram) {
         if (tid < B) n_ban[tid] = 0;
-    } else {           // (block-uniform) lane l holds y_l; one lane per start j = 1 … p − n of an earlier gram
+    } else if constexpr (!PARA) {   // (block-uniform) lane l holds y_l; one lane per start j = 1 … p − n of an earlier gram
         const int n = a.ngram, s0 = pl - n + 1;   // the (n − 1)-suffix y_{s0} … y_pos of the new gram
         for (int h = __builtin_amdgcn_readfirstlane(wave); h < B; h += kBeamThreads / 64) {
             if (a.finished[r0 + h]) {             // (wave-uniform; the row's wave is the only writer of n_ban[h] before the barrier)
@@ -111,6 +130,45 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
             const unsigned long long m = __ballot(banned);
             if (banned) ban[h][__popcll(m & ((1ull << lane) - 1ull))] = w;
             if (lane == 0) n_ban[h] = __popcll(m);
+        }
+    } else {           // paragraph scope: the row's own pass as above, then one wave-wide pass per earlier sentence, into the bitmap
+        const int n = a.ngram, s0 = pl - n + 1;
+        const unsigned long long gm = (1ull << n) - 1ull;      // (n <= 63)
+        const int h_first = a.hdesc[2 * t], h_count = a.hdesc[2 * t + 1];
+        for (int h = __builtin_amdgcn_readfirstlane(wave); h < B; h += kBeamThreads / 64) {
+            if (a.finished[r0 + h]) {
+                if (lane == 0) n_ban[h] = 0;
+                continue;
+            }
+            unsigned* bits = ban_bits[h];
+            const int nw = (min(a.row_c[r0 + h], kBanCols) + 31) >> 5;
+            for (int k = lane; k < nw; k += 64) bits[k] = 0u;
+            const int y = lane <= a.pos ? a.ext_in[(size_t)(r0 + h) * a.ld_tok + lane] : -1;
+            const bool ex = excluded(a, y);
+            if (__ballot(ex && lane >= s0 && lane <= a.pos) != 0ull) {      // an excluded token in the suffix saves every gram
+                if (lane == 0) n_ban[h] = 0;
+                continue;
+            }
+            bool match = lane >= 1 && lane <= pl - n;
+            for (int k = 0; k < n - 1; ++k) match &= __shfl(y, lane + k, 64) == __shfl(y, s0 + k, 64);
+            int w = __shfl(y, lane + n - 1, 64);
+            const bool w_ex = __shfl((int)ex, lane + n - 1, 64) != 0;      // (every lane shuffles: a source lane must be active)
+            bool banned = match && !w_ex;
+            int nb = __popcll(__ballot(banned));
+            if (banned && w >= 0 && w < kBanCols) atomicOr(&bits[w >> 5], 1u << (w & 31));
+            for (int q = 0; q < h_count; ++q) {   // lane j holds z_j of the earlier sentence's caption
+                const int z = lane < a.ld_tok ? a.hist[(size_t)(h_first + q) * a.ld_tok + lane] : a.pad;
+                const unsigned long long stop = __ballot(lane >= 1 && (z == a.eos || z == a.pad));
+                const int last = stop ? __ffsll((long long)stop) - 2 : a.ld_tok - 1;      // the last word position L
+                const unsigned long long vm = __ballot(lane >= 1 && lane <= last && z != a.bos);
+                match = lane >= 1 && lane + n - 1 <= last && ((vm >> lane) & gm) == gm;
+                for (int k = 0; k < n - 1; ++k) match &= __shfl(z, lane + k, 64) == __shfl(y, s0 + k, 64);
+                w = __shfl(z, lane + n - 1, 64);
+                banned = match && !excluded(a, w);
+                nb += __popcll(__ballot(banned));
+                if (banned && w >= 0 && w < kBanCols) atomicOr(&bits[w >> 5], 1u << (w & 31));
+            }
+            if (lane == 0) n_ban[h] = nb;
         }
     }
     __syncthreads();
@@ -145,6 +203,9 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
         if (nb == 0) {
             for (int c = lane; c < C; c += 64)
                 if (c != a.unk && c != skip_eos) topb_insert<B>(val, idx, row[c], c);
+        } else if constexpr (PARA) {
+            for (int c = lane; c < C; c += 64)
+                if (c != a.unk && c != skip_eos) topb_insert_bits<B>(val, idx, row[c], c, ban_bits[h]);
         } else {
             for (int c = lane; c < C; c += 64)
                 if (c != a.unk && c != skip_eos) topb_insert_ban<B>(val, idx, row[c], c, ban[h], nb);
@@ -246,6 +307,22 @@ __global__ __launch_bounds__(256) void beam_finalize_kernel(const float* __restr
     }
 }
 
+template <bool PARA>
+int launch_beam_step(const BeamArgs& a, int n_sent, int beam, hipStream_t stream) {
+    const dim3 grid(n_sent), block(kBeamThreads);
+    switch (beam) {
+        case 1: hipLaunchKernelGGL((beam_step_kernel<1, PARA>), grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((beam_step_kernel<2, PARA>), grid, block, 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((beam_step_kernel<3, PARA>), grid, block, 0, stream, a); break;
+        case 4: hipLaunchKernelGGL((beam_step_kernel<4, PARA>), grid, block, 0, stream, a); break;
+        case 5: hipLaunchKernelGGL((beam_step_kernel<5, PARA>), grid, block, 0, stream, a); break;
+        case 6: hipLaunchKernelGGL((beam_step_kernel<6, PARA>), grid, block, 0, stream, a); break;
+        case 7: hipLaunchKernelGGL((beam_step_kernel<7, PARA>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((beam_step_kernel<8, PARA>), grid, block, 0, stream, a); break;
+    }
+    return svpc_check_launch("beam_step");
+}
+
 }  // namespace
 
 extern "C" {
@@ -263,19 +340,27 @@ int svpc_beam_step_ctl(const float* scores, int ld, const int* row_c, const int*
     SVPC_REQUIRE(lp == nullptr || len != nullptr, "beam_step: a length penalty needs the length array");
     SVPC_REQUIRE(excl == nullptr || excl_v > 0, "beam_step: the exclusion bitmap needs its id count");
     BeamArgs a{scores, ld, row_c, row_x, pos, logits, unk, eos, pad, slot_rows, cum, finished, text_in, ext_in, rows_in,
-               text_out, ext_out, rows_out, ld_tok, parent, next_ext, next_model, min_len, ngram, excl, excl_v, lp, len};
-    const dim3 grid(n_sent), block(kBeamThreads);
-    switch (beam) {
-        case 1: hipLaunchKernelGGL(beam_step_kernel<1>, grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL(beam_step_kernel<2>, grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL(beam_step_kernel<3>, grid, block, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL(beam_step_kernel<4>, grid, block, 0, stream, a); break;
-        case 5: hipLaunchKernelGGL(beam_step_kernel<5>, grid, block, 0, stream, a); break;
-        case 6: hipLaunchKernelGGL(beam_step_kernel<6>, grid, block, 0, stream, a); break;
-        case 7: hipLaunchKernelGGL(beam_step_kernel<7>, grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL(beam_step_kernel<8>, grid, block, 0, stream, a); break;
-    }
-    return svpc_check_launch("beam_step");
+               text_out, ext_out, rows_out, ld_tok, parent, next_ext, next_model, min_len, ngram, excl, excl_v, lp, len, nullptr, nullptr, 0};
+    return launch_beam_step<false>(a, n_sent, beam, stream);
+}
+
+int svpc_beam_step_para(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                        int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                        int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
+                        int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, const int* hist, const int* hist_desc,
+                        int bos, hipStream_t stream) {
+    if (n_sent == 0) return 0;
+    SVPC_REQUIRE(beam >= 1 && beam <= kBeamMax, "beam_step_para: beam width must be 1..8");
+    SVPC_REQUIRE(pos >= 0 && pos + 1 < ld_tok && pos + 1 < slot_rows, "beam_step_para: position pos + 1 must lie inside the token / ancestry rows");
+    SVPC_REQUIRE(text_in != text_out && ext_in != ext_out && rows_in != rows_out, "beam_step_para: the token and ancestry tables are ping-pong pairs");
+    SVPC_REQUIRE(min_len >= 0 && min_len < ld_tok && ngram >= 1 && ngram < ld_tok, "beam_step_para: min length 0..ld_tok-1, n-gram size 1..ld_tok-1");
+    SVPC_REQUIRE(ld_tok <= 64, "beam_step_para: n-gram blocking holds a caption's ids in one wave (ld_tok <= 64)");
+    SVPC_REQUIRE(lp == nullptr || len != nullptr, "beam_step_para: a length penalty needs the length array");
+    SVPC_REQUIRE(excl == nullptr || excl_v > 0, "beam_step_para: the exclusion bitmap needs its id count");
+    SVPC_REQUIRE(hist != nullptr && hist_desc != nullptr, "beam_step_para: the history matrix and its descriptors are required");
+    BeamArgs a{scores, ld, row_c, row_x, pos, logits, unk, eos, pad, slot_rows, cum, finished, text_in, ext_in, rows_in,
+               text_out, ext_out, rows_out, ld_tok, parent, next_ext, next_model, min_len, ngram, excl, excl_v, lp, len, hist, hist_desc, bos};
+    return launch_beam_step<true>(a, n_sent, beam, stream);
 }
 
 int svpc_beam_step(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,

@@ -2527,11 +2527,16 @@ BEAM_MAX = 8
 LENGTH_PENALTIES = ("none", "avg", "wu")
 
 
+BLOCK_SCOPES = ("sentence", "paragraph")
+
+
 def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none",
-                        length_penalty_alpha=0.0, n_best=None):
+                        length_penalty_alpha=0.0, n_best=None, block_ngram_scope="sentence", max_cols=None):
     """The decoding controls of a beam decode over Lt = ``lt`` positions and ``vocab`` text ids, checked on the host (ValueError) and
-    normalised → dict(block_ngram_repeat, exclusion_tokens (sorted tuple), min_length, length_penalty_name, length_penalty_alpha
-    [, n_best]).  n: 0 … Lt − 1 (and Lt ≤ 64 when n > 0); m: 0 … Lt − 1; exclusion ids in [0, vocab); alpha finite ≥ 0; n_best 1 … beam."""
+    normalised → dict(block_ngram_repeat, exclusion_tokens (sorted tuple), min_length, length_penalty_name, length_penalty_alpha,
+    block_ngram_scope [, n_best]).  n: 0 … Lt − 1 (and Lt ≤ 64 when n > 0); m: 0 … Lt − 1; exclusion ids in [0, vocab); alpha finite ≥ 0;
+    n_best 1 … beam; scope ``sentence`` or ``paragraph`` (needs n > 0 and score rows of at most SAMPLE_COLS_MAX columns: ``max_cols``, the
+    widest row V + X, default ``vocab``)."""
     def as_int(name, v):
         if isinstance(v, bool) or not isinstance(v, numbers.Integral):
             raise ValueError("%s must be an integer, got %r" % (name, v))
@@ -2557,13 +2562,28 @@ def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_to
         raise ValueError("length_penalty_alpha must be a number, got %r" % (length_penalty_alpha,))
     if not math.isfinite(alpha) or alpha < 0:
         raise ValueError("length_penalty_alpha must be finite and >= 0, got %r" % (length_penalty_alpha,))
-    out = dict(block_ngram_repeat=n, exclusion_tokens=excl, min_length=m, length_penalty_name=name, length_penalty_alpha=alpha)
+    scope = block_ngram_scope if block_ngram_scope is not None else "sentence"
+    if scope not in BLOCK_SCOPES:
+        raise ValueError("block_ngram_scope must be one of %s, got %r" % (", ".join(BLOCK_SCOPES), block_ngram_scope))
+    if scope == "paragraph":
+        if n == 0:
+            raise ValueError("block_ngram_scope='paragraph' needs block_ngram_repeat > 0 (there is nothing to block)")
+        check_paragraph_cols(vocab if max_cols is None else max_cols)
+    out = dict(block_ngram_repeat=n, exclusion_tokens=excl, min_length=m, length_penalty_name=name, length_penalty_alpha=alpha,
+               block_ngram_scope=scope)
     if n_best is not None:
         k = as_int("n_best", n_best)
         if beam is None or not 1 <= k <= beam:
             raise ValueError("n_best must be 1..%s (the beam width), got %d" % (beam, k))
         out["n_best"] = k
     return out
+
+
+def check_paragraph_cols(max_cols):
+    """paragraph-scope blocking keeps a row's bans as a bitmap of SAMPLE_COLS_MAX columns: wider score rows (V + X) are refused"""
+    if int(max_cols) > SAMPLE_COLS_MAX:
+        raise ValueError("block_ngram_scope='paragraph' reads score rows of at most %d columns (vocabulary + copied words), got %d"
+                         % (SAMPLE_COLS_MAX, max_cols))
 
 
 def length_penalty_table(name, alpha, lt):
@@ -2587,13 +2607,16 @@ def exclusion_bitmap(tokens, vocab, device):
 
 
 def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows, *, length=None,
-              min_length=0, block_ngram_repeat=0, exclusion=None, lp=None):
+              min_length=0, block_ngram_repeat=0, exclusion=None, lp=None, history=None):
     """One beam-search selection step (svpc_beam_step) over ``scores`` (T·beam, ≥ C) — probabilities, or logits when ``logits``.
     ``cum`` (T·beam,) fp32 and ``finished`` (T·beam,) int32 are updated in place; ``toks_in`` / ``toks_out`` = (text, ext, key_rows): the
     ping-pong (T·beam, Lt) int32 id matrices and KV-cache ancestry tables, the children's written for positions ≤ pos + 1.
     Decoding controls (keyword-only; any given → svpc_beam_step_ctl): ``length`` (T·beam,) int32 hypothesis lengths, updated in place;
     ``min_length`` m; ``block_ngram_repeat`` n; ``exclusion`` = (bitmap of ``exclusion_bitmap``, vocab); ``lp`` float64 (Lt,) table of
     ``length_penalty_table`` (needs ``length``).
+    Paragraph scope (``history`` given → svpc_beam_step_para; needs n ≥ 1 and rows of at most SAMPLE_COLS_MAX columns): ``history`` =
+    (table, desc, bos): ``table`` a contiguous int32 (rows, Lt) matrix of earlier sentences' chosen extended ids on the scores' device,
+    ``desc`` 2·T host ints (an Idx or a list) — sentence t's history is rows desc[2t] … desc[2t] + desc[2t + 1] − 1 — and the BOS id.
     → (parent, next_ext, next_model) int32 (T·beam,)."""
     if not 1 <= beam <= BEAM_MAX:
         raise ValueError("beam_step: beam width must be 1..%d" % BEAM_MAX)
@@ -2609,7 +2632,21 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
             raise ValueError("beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
     if not 0 <= pos < lt - 1 or slot_rows < lt:
         raise ValueError("beam_step: position %d outside the %d-column tables" % (pos, lt))
-    ctl = length is not None or min_length or block_ngram_repeat or exclusion is not None or lp is not None
+    ctl = length is not None or min_length or block_ngram_repeat or exclusion is not None or lp is not None or history is not None
+    if history is not None:
+        table, desc, bos = history
+        desc = as_idx(desc)
+        if int(block_ngram_repeat) < 1 or lt > 64:
+            raise ValueError("beam_step: paragraph scope needs block_ngram_repeat >= 1 and Lt <= 64")
+        if (table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != lt or not table.is_contiguous()
+                or table.device != scores.device):
+            raise ValueError("beam_step: the history must be a contiguous int32 (rows, Lt) matrix on the scores' device")
+        d = desc.host
+        if len(d) != 2 * (R // beam) or any(c < 0 or f < 0 or f + c > table.shape[0] for f, c in zip(d[0::2], d[1::2])):
+            raise ValueError("beam_step: the history descriptors must be (first row, count) pairs inside the history, one per sentence")
+        rc = as_idx(row_c).host
+        if rc and max(rc) > SAMPLE_COLS_MAX:
+            raise ValueError("beam_step: paragraph scope reads rows of at most %d columns" % SAMPLE_COLS_MAX)
     if ctl:
         if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
             raise ValueError("beam_step: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
@@ -2631,6 +2668,14 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
     parent = torch.empty(R, dtype=torch.int32, device=dev)
     nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
     nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    if history is not None:
+        bits, vocab = exclusion if exclusion is not None else (None, 0)
+        _lib.call("beam_step_para", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam,
+                  int(beam), int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
+                  _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
+                  int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _p(table), _p(desc.dev(dev)), int(bos),
+                  _stream())
+        return parent, nxt_ext, nxt
     if ctl:
         bits, vocab = exclusion if exclusion is not None else (None, 0)
         _lib.call("beam_step_ctl", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),

@@ -52,6 +52,24 @@ default to off, and with every control off nothing changes (same ids, scores, la
 - greedy (``use_beam=False``) with any control on runs the width-1 beam with those controls; with none, the greedy path is untouched;
 - every argument is checked on the host (ValueError) before any device work.  Each setting has its own prepared plan and captured graph.
 
+**Paragraph-scope blocking** (``block_ngram_scope``: ``"sentence"``, the default and the rule above, or ``"paragraph"``; resolved like the
+other controls, not taken by ``translate_batch_sample``).  The reference scores a video's captions as one paragraph (its repetition metric
+counts the n-grams of all of a video's sentences together, none spanning two sentences), so ``"paragraph"`` also blocks the grams of the
+video's earlier captions:
+
+- a video's sentences are taken in index order s = 0 … S_b − 1 (timestamp order); the *words* of a decoded sentence are the extended ids
+  of its chosen caption (row 0 in final-key order) at positions 1 … L, L + 1 being its first EOS or PAD (L = Lt − 1 when it has none),
+  BOS excepted; a copied OOV word (id ≥ V) is its own word.  A gram is n consecutive positions that are all words, so none spans two
+  sentences;
+- candidate (h, w) at position p ≥ n of sentence s is also banned when (y_{p−n+1} … y_pos, w) equals a gram of a sentence s′ < s of the
+  same video and no token of it is in ``exclusion_tokens``; the within-hypothesis ban applies as well, and everything else (skipped like
+  UNK, ``video`` mode's log-sum-exp, ``min_length``, the length penalty, n-best order, fewer than B candidates) is as above;
+- so sentence s is decoded after sentences 0 … s − 1 of its video, conditioned on their chosen captions: the decoding iterations run in
+  rounds, round s over sentence s of every video with S_b > s.  Sentence 0, and every video with S_b = 1, gets what ``"sentence"`` gives;
+  with n-best, later sentences see row 0; greedy with it is the width-1 beam with it;
+- ValueError on the host for an unknown scope, ``"paragraph"`` with ``block_ngram_repeat == 0``, and ``"paragraph"`` with score rows wider
+  than ``ops.SAMPLE_COLS_MAX`` = 4096 columns (V + X: the kernel keeps a row's bans as a bitmap of that many columns).
+
 The per-layer KV caches hold one slot of Lt rows per hypothesis; a row is written once, into the slot of the hypothesis that computes it,
 and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that the attention reads through (no cache copy per step).
 
@@ -83,12 +101,13 @@ and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that t
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
 from .model import BatchPlan, _Ctx
 from .ops import check_beam_controls, check_sampling, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
-from .ops_common import ACT_RELU, Idx, SeqInfo
+from .ops_common import ACT_RELU, BulkUpload, Idx, SeqInfo
 from .synthetic import BOS, EOS, PAD, UNK
 
 
@@ -136,11 +155,12 @@ class Translator(object):
         input_masks[text_mask] = 0
         return input_ids, input_masks
 
-    CONTROLS = dict(block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none", length_penalty_alpha=0.0)
+    CONTROLS = dict(block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none", length_penalty_alpha=0.0,
+                    block_ngram_scope="sentence")
 
     def _controls(self, kw, beam=None, n_best=None):
         """The decoding controls: ``opt`` attributes overridden by keyword arguments, checked (ValueError) → (normalised dict, key):
-        key None when every control is off (the uncontrolled decode)."""
+        key None when every control is off (the uncontrolled decode); paragraph scope appends ``"paragraph"`` to the key."""
         unknown = set(kw) - set(self.CONTROLS)
         if unknown:
             raise TypeError("unknown decoding control(s): %s" % ", ".join(sorted(unknown)))
@@ -149,6 +169,8 @@ class Translator(object):
         on = c["block_ngram_repeat"] > 0 or c["min_length"] > 0 or c["length_penalty_name"] != "none"
         key = (c["block_ngram_repeat"], c["exclusion_tokens"] if c["block_ngram_repeat"] else (), c["min_length"], c["length_penalty_name"],
                c["length_penalty_alpha"] if c["length_penalty_name"] == "wu" else 0.0) if on else None
+        if c["block_ngram_scope"] == "paragraph":
+            key = key + ("paragraph",)
         return c, key
 
     def translate_batch(self, model_inputs, use_beam=False, recurrent=True, untied=False, xl=False, mtrans=False, **controls):
@@ -213,6 +235,8 @@ class Translator(object):
     def _translate_beam(self, model_inputs, B, ctl, key, n_best):
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
          ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
+        if ctl["block_ngram_scope"] == "paragraph" and self.model_config.model_mode != "video":     # (score rows of V + X columns)
+            ops.check_paragraph_cols(self.model_config.vocab_size + max([len(d) for d in oov_word_dict] + [0]))
         return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids,
                                ingr_sep_masks, ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=B, ctl=(ctl, key),
                                n_best=n_best)
@@ -255,6 +279,8 @@ class Translator(object):
                     exclusion=(exclusion_bitmap(c["exclusion_tokens"], V, dev), V) if n and c["exclusion_tokens"] else None,
                     lp=(torch.tensor(length_penalty_table(c["length_penalty_name"], c["length_penalty_alpha"], Lt), dtype=torch.float64,
                                      device=dev) if c["length_penalty_name"] != "none" else None))
+                if c["block_ngram_scope"] == "paragraph":
+                    prep["para"] = self._paragraph_rounds(model, plan, dicts, c_list, n_oov, beam, Lt, dev)
             if sample is not None:
                 # sampling: every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed
                 # source (fixed, value) and the seed the decode used are captured device words
@@ -268,6 +294,39 @@ class Translator(object):
             self._preps.clear()
         self._preps[key] = prep
         return prep
+
+    @staticmethod
+    def _paragraph_rounds(model, plan, dicts, c_list, n_oov, B, Lt, dev):
+        """The round tables of a paragraph-scope decode (round s: sentence s of every video with S_b > s, N_s·B hypothesis rows), all
+        sent in one copy: per round its sentences' global indices (int64, for the scatters; int32, for the row gathers), the memory rows
+        of its sentences, the pointer plan and OOV counts of its rows, the history descriptors (first top-1 row of the video, count s),
+        and the attention segmentations."""
+        steps, off = plan.h_step_len, plan.h_step_off
+        n_mem = model._n_mem()
+        ne = plan.step_ne.host
+        up = BulkUpload(dev)
+        rounds = []
+        for s_ in range(max(steps)):
+            vids = [b for b in range(plan.N) if steps[b] > s_]
+            sent = [off[b] + s_ for b in vids]
+            Ns = len(sent)
+            TB = Ns * B
+            row_vid = Idx([b for b in vids for _ in range(B)])
+            rd = dict(n=Ns, step_ne=Idx([ne[t] for t in sent]), row_vid=row_vid, row_xb=Idx([n_oov[b] for b in row_vid.host]),
+                      desc=Idx([v for b in vids for v in (off[b], s_)]), sent32=Idx(sent),
+                      mem_rows=Idx([t * n_mem + j for t in sent for j in range(n_mem)]),
+                      seq_cross=SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, None),
+                      seq_self=[SeqInfo.uniform(TB, 1, i + 1, None) for i in range(Lt - 1)])
+            rd["plb"] = model._ptr_plan(dicts, c_list, B, rd["step_ne"], row_vid)
+            up.add(np.asarray(sent, dtype=np.int64).view(np.int32), sink=lambda t, rd=rd: rd.__setitem__("sent64", t.view(torch.int64)))
+            for v in (rd["step_ne"], row_vid, rd["row_xb"], rd["desc"], rd["sent32"], rd["mem_rows"]) + tuple(
+                    rd["plb"][k] for k in ("csr_off", "csr_ent", "csr_id", "csr_w", "row_c")):
+                up.add_idx(v)
+            for sq in [rd["seq_cross"]] + rd["seq_self"]:
+                up.add_seq(sq)
+            rounds.append(rd)
+        up.flush()
+        return dict(rounds=rounds, rows_max=max(rd["n"] for rd in rounds) * B)
 
     def _text_table(self, model, Lt, cx, dev):
         """(Lt, V, D): text_embeddings(token v at position p) for every (p, v) — inference weights are constant, so the embedding stack
@@ -323,6 +382,10 @@ class Translator(object):
             bank = None
 
         stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
+        if prep.get("para") is not None:
+            out = self._paragraph_iterations(model, prep, mem, bank, cx, tab=self._text_table(model, Lt, cx, dev))
+            stamp()
+            return out
         if prep["beam"]:
             out = self._beam_iterations(model, prep, mem, bank, cx, tab=self._text_table(model, Lt, cx, dev))
             stamp()
@@ -405,14 +468,7 @@ class Translator(object):
         plb, row_xb = prep["plb"], prep["row_xb"]
         samp = prep.get("sample")
         if samp is None:
-            # ping-pong (text ids, extended ids, KV-cache ancestry) tables: children are written from their parents' rows
-            toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
-            toks[0][0][:, 0] = BOS
-            toks[0][1][:, 0] = BOS
-            toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
-            cum = torch.zeros(T, B, dtype=torch.float32, device=dev)
-            cum[:, 1:] = float("-inf")                                             # the first step: beam 0 alone
-            cum = cum.view(TB)
+            toks, cum = self._beam_start(T, B, Lt, dev)
         else:
             # sampling: one (text ids, extended ids) pair written in place; every sample starts alive at BOS
             text = torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev)
@@ -431,13 +487,7 @@ class Translator(object):
             seq_self = prep["seq_self_b"].get(i)
             if seq_self is None:
                 seq_self = prep["seq_self_b"][i] = SeqInfo.uniform(TB, 1, i + 1, dev)
-            x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
-            for layer, cache, kv in zip(layers, caches, mem_kv):
-                x = layer.step(x, i, Lt, cache, kv, seq_self, seq_cross, cx, key_rows=rows, q_group=B)
-            if mode == "video":
-                scores = model.decoder_classifier.run(x, cx.eps)          # raw logits: the step score is their log_softmax
-            else:
-                scores, _ = model._lm_probs(x, bank, plb, cx, proj=proj)
+            scores = self._hyp_scores(model, cx, tab, nxt, i, caches, mem_kv, seq_self, seq_cross, rows, B, bank, plb, proj)
             if samp is not None:
                 _, nxt = ops.sample_step(scores, plb["row_c"], row_xb, i, mode == "video", UNK, EOS, PAD, cum, fin, length, text, ext,
                                          prep["seed_used"], temp=samp["temp"], topk=samp["topk"], topp=samp["topp"],
@@ -452,6 +502,78 @@ class Translator(object):
         if ranked:           # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
             return ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
         return ops.beam_finalize(cum, toks[(Lt - 1) % 2][1], B)
+
+    @staticmethod
+    def _beam_start(n_sent, B, Lt, dev):
+        """the first step's tables of a beam decode over n_sent·B hypothesis rows: the ping-pong (text ids, extended ids, KV-cache ancestry)
+        pairs — children are written from their parents' rows — with BOS and the row's own slot at position 0, and cum (beam 0 alone)"""
+        TB = n_sent * B
+        toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
+        toks[0][0][:, 0] = BOS
+        toks[0][1][:, 0] = BOS
+        toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
+        cum = torch.zeros(n_sent, B, dtype=torch.float32, device=dev)
+        cum[:, 1:] = float("-inf")                                             # the first step: beam 0 alone
+        return toks, cum.view(TB)
+
+    @staticmethod
+    def _hyp_scores(model, cx, tab, nxt, i, caches, mem_kv, seq_self, seq_cross, rows, B, bank, plb, proj):
+        """one decoding iteration over hypothesis rows → their score rows: the text embedding of tokens ``nxt`` at position i, the layers
+        over each row's ancestry ``rows`` in the KV caches (B rows per sentence share its memory K|V), then the head — raw logits in
+        ``video`` mode (the step score is their log_softmax) — or the pointer-generator's probabilities"""
+        x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
+        for layer, cache, kv in zip(model.decoder.layer, caches, mem_kv):
+            x = layer.step(x, i, model.config.max_t_len, cache, kv, seq_self, seq_cross, cx, key_rows=rows, q_group=B)
+        if model.config.model_mode == "video":
+            return model.decoder_classifier.run(x, cx.eps)
+        return model._lm_probs(x, bank, plb, cx, proj=proj)[0]
+
+    def _paragraph_iterations(self, model, prep, mem, bank, cx, tab):
+        """A paragraph-scope beam decode: the Lt − 1 selection steps (svpc_beam_step_para) run once per round, round s over the N_s·B
+        rows of sentence s of every video with S_b > s, reading the chosen captions of rounds 0 … s − 1 from the decode's (T, Lt) top-1
+        matrix.  Each round gathers its sentences' rows of the memory K|V projection, the pointer bank and its projection; the per-layer
+        KV caches are sized for the largest round and reused (a round reads only rows it wrote).  → (ids (T, B, Lt) int32, cum (T, B)
+        fp32, len (T, B) int32) in final-key order, as ``_beam_iterations`` with controls."""
+        cfg = model.config
+        mode = cfg.model_mode
+        B, T = prep["beam"], prep["T"]
+        dev = mem.device
+        Lt, D = cfg.max_t_len, cfg.hidden_size
+        layers = model.decoder.layer
+        para, ctl = prep["para"], prep["ctl"]
+        caches = [torch.zeros(para["rows_max"] * Lt, 2 * D, dtype=torch.float32, device=dev) for _ in layers]
+        st = model.decoder.stacked_memory_kv()
+        wide = [ops.linear(mem, st[0], st[1])] if st is not None else [layer.memory_kv(mem) for layer in layers]
+        proj = model.bank_projection(bank) if bank is not None else None
+        ids = torch.full((T, B, Lt), PAD, dtype=torch.int32, device=dev)
+        cums = torch.empty(T, B, dtype=torch.float32, device=dev)
+        lens = torch.empty(T, B, dtype=torch.int32, device=dev)
+        top1 = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)        # the chosen captions: the later rounds' history
+        for rd in para["rounds"]:
+            Ns = rd["n"]
+            TB = Ns * B
+            mem_rows, sent = rd["mem_rows"].dev(dev), rd["sent32"].dev(dev)
+            kv = [ops.take_rows_f32(w, mem_rows) for w in wide]
+            mem_kv = ops.split_cols(kv[0], len(layers)) if st is not None else kv
+            bank_r = ops.take_rows_f32(bank.reshape(T, -1), sent).view(Ns, *bank.shape[1:]) if bank is not None else None
+            proj_r = ops.take_rows_f32(proj.reshape(T, -1), sent).view(Ns, *proj.shape[1:]) if proj is not None else None
+            toks, cum = self._beam_start(Ns, B, Lt, dev)
+            fin = torch.zeros(TB, dtype=torch.int32, device=dev)
+            length = torch.zeros(TB, dtype=torch.int32, device=dev)
+            nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
+            cache_r = [c[:TB * Lt] for c in caches]
+            for i in range(Lt - 1):
+                t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
+                scores = self._hyp_scores(model, cx, tab, nxt, i, cache_r, mem_kv, rd["seq_self"][i], rd["seq_cross"], t_in[2], B, bank_r,
+                                          rd["plb"], proj_r)
+                _, _, nxt = ops.beam_step(scores, rd["plb"]["row_c"], rd["row_xb"], B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out,
+                                          Lt, length=length, history=(top1, rd["desc"], BOS), **ctl)
+            r_ids, r_cum, r_len = ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
+            ids.index_copy_(0, rd["sent64"], r_ids)
+            cums.index_copy_(0, rd["sent64"], r_cum)
+            lens.index_copy_(0, rd["sent64"], r_len)
+            top1.index_copy_(0, rd["sent64"], r_ids[:, 0])
+        return ids, cums, lens
 
     def _seed_word_on(self, dev):
         """the sampling decodes' seed word (int64 (1,) on ``dev``): drawn once from torch's default generator, then advanced on the device
