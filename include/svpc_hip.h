@@ -540,6 +540,25 @@ int svpc_sample_step(const float* scores, int ld, const int* row_c, const int* r
 /* the seed of one sampling decode, on the device: src = (fixed, value); fixed != 0: *used = value; otherwise *used is drawn from the
  * decode's seed word *word, which advances (consecutive replays of one captured decode draw different streams) */
 int svpc_sample_seed(const long long* src, long long* word, long long* used, svpc_stream_t stream);
+/* ---- evaluation tail of a decode: the caption the reference submits and its repetition / diversity counts, on the device
+ *      (recursive_caption_dataset.py:472-500 convert_ids_to_sentence, src/translate.py:27-42 remove_dup, densevid_eval/evaluateRepetition.py,
+ *      evaluateCaptionsDiversity.py:219-282, get_caption_stat.py; the reference copies every sentence to the host, translate.py:81-82).
+ * svpc_caption_clean: id row r = the lt ids at ids + (r·row_stride + row_pick)·ld (int64 when ids64, else int32; row_stride / row_pick
+ * take row k of (T, K, Lt) n-best / sample outputs), lt <= 64.  Clean caption: the ids without pad and ignore, without the first of those,
+ * up to (not including) the first eos, runs of one id collapsed to one (remove_dup != 0).  Out: words (n_rows, lt) int32, the caption
+ * left-aligned and pad-filled, and len (n_rows,) int32 (0 … lt − 1). */
+int svpc_caption_clean(const void* ids, int ids64, long long ld, int row_stride, int row_pick, int n_rows, int lt, long long pad,
+                       long long eos, long long ignore, int remove_dup, int* words, int* len, svpc_stream_t stream);
+/* per video b (rows vid_off[b] … vid_off[b + 1] − 1 of words / len, at most 4096 / lt rows — the host checks; a larger video's row is −1):
+ * its repetition words are each clean caption without a final `period` word and without any `comma` word (INT_MIN: no such id); an n-gram is
+ * n consecutive repetition words of one caption.  counts (n_vid, 12) int32 = total_1..4 (n-grams), distinct_1..4 (different ones, compared
+ * id by id), n_sen, n_words (clean words, before the punctuation rule), n_empty (clean captions of length 0), n_copied (clean words >= vocab).
+ * vocab_bits (or NULL): bit w of the bitmap is set (atomic OR) for every clean word 0 <= w < vocab. */
+int svpc_caption_ngram_counts(const int* words, const int* len, const int* vid_off, int n_vid, int lt, int period, int comma, int vocab,
+                              int* counts, unsigned* vocab_bits, svpc_stream_t stream);
+/* acc[0..12] += Σ_b (re_1..4, div_1..4, 1, n_sen, n_words, n_empty, n_copied) over the n_vid rows of counts, re_n = (total_n − distinct_n) /
+ * total_n (0 when total_n = 0), div_n = distinct_n / total_1 (0 when total_1 = 0); fp64, summed in a fixed order (deterministic). */
+int svpc_decode_metric_accum(const int* counts, int n_vid, double* acc, svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

@@ -4,12 +4,18 @@ reference: src/train.py:32-38 (cal_performance: correct next-word predictions ov
 hits / gold positives / predicted positives of the entity and action probabilities at threshold 0.5), :51-68 (compute_total_f1),
 :150-180 (per-step accumulation with ≈10 ``.item()`` host synchronisations).  Here the nine running sums live in one device buffer
 updated by two small kernels per video; ``result()`` is the only host read-back.
+
+``DecodeMetrics`` is the evaluation-side counterpart: the captions the reference submits and its repetition / diversity numbers
+(src/translate.py:27-42 and :81-83, recursive_caption_dataset.py:472-500, densevid_eval/evaluateRepetition.py,
+evaluateCaptionsDiversity.py:219-282, get_caption_stat.py) from the translator's id matrices, three launches per batch and no host
+synchronisation until ``result()``.
 """
 from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, ops
+from .synthetic import EOS, PAD
 
 IGNORE = -1
 
@@ -72,3 +78,76 @@ class TrainMetrics:
                     loss_per_word=(v[8] / n_word) if n_word else 0.0, accuracy=(n_corr / n_word) if n_word else 0.0,
                     entity=compute_total_f1(v[2], v[3], v[4]), action=compute_total_f1(v[5], v[6], v[7]),
                     counts=v[:8])
+
+
+class DecodeMetrics:
+    """Running repetition / diversity / caption statistics of an evaluation epoch, kept on the device.
+
+    ``update(dec_seq_list, row=0)`` takes what ``Translator.translate_batch`` / ``translate_batch_beam`` (first element) /
+    ``translate_batch_nbest`` / ``translate_batch_sample`` return: per video an (S_b, Lt) or (S_b, K, Lt) id tensor (``row`` picks one of
+    the K).  Clean caption → per-video n-gram counts → accumulator: three launches for the whole batch, no copy when the list is
+    consecutive views of one buffer (one ``torch.cat`` otherwise), nothing uploaded for a recurring (S_b) structure — so ``update`` can be
+    captured once its structure has been seen.  ``result()`` is the only read-back.
+
+    accumulator: [Σ re1..4, Σ div1..4, videos, sentences, clean words, empty captions, copied words (id ≥ V)]; ``vocab_bits`` marks the
+    ids < V seen among the clean words.  ``last_counts``: the last update's (N, 12) int32 per-video counts (total_1..4, distinct_1..4,
+    n_sen, n_words, n_empty, n_copied)."""
+
+    FIELDS = ("re1", "re2", "re3", "re4", "div1", "div2", "div3", "div4")
+
+    def __init__(self, vocab_size, device="cuda", pad=PAD, eos=EOS, period_id=None, comma_id=None, remove_dup=True):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.V = int(vocab_size)
+        if self.V < 1:
+            raise ValueError("vocab_size must be >= 1, got %r" % (vocab_size,))
+        ops.check_caption_metrics(1, period_id=period_id, comma_id=comma_id)
+        self.pad, self.eos, self.period_id, self.comma_id, self.remove_dup = int(pad), int(eos), period_id, comma_id, bool(remove_dup)
+        self.acc = torch.zeros(13, dtype=torch.float64, device=self.device)
+        self.vocab_bits = torch.zeros((self.V + 31) // 32, dtype=torch.int32, device=self.device)
+        self.last_counts = None
+        self._offs = {}
+
+    def reset(self):
+        self.acc.zero_()
+        self.vocab_bits.zero_()
+        self.last_counts = None
+
+    def _vid_off(self, steps, dev):
+        """the (N + 1,) int32 table of the videos' first rows: uploaded once per (S_b) structure"""
+        key = (tuple(steps), str(dev))
+        t = self._offs.get(key)
+        if t is None:
+            off = [0]
+            for s in steps:
+                off.append(off[-1] + s)
+            if len(self._offs) > 32:
+                self._offs.clear()
+            t = self._offs[key] = torch.tensor(off, dtype=torch.int32, device=dev)
+        return t
+
+    def update(self, dec_seq_list, row=0):
+        ids, steps = ops.stack_captions(dec_seq_list)
+        lt = ids.shape[-1]
+        ops.check_caption_metrics(lt, ids.dtype, steps=steps, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
+        if not ids.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
+        words, ln = ops.clean_captions(ids, self.pad, self.eos, IGNORE, self.remove_dup, row=row)
+        counts = ops.caption_ngram_counts(words, ln, self._vid_off(steps, ids.device), self.V, self.period_id, self.comma_id,
+                                          vocab_bits=self.vocab_bits, steps=steps)
+        ops.decode_metric_accum(counts, self.acc)
+        self.last_counts = counts
+        return counts
+
+    def result(self):
+        """The single host read-back → re1..re4, div1..div4 (means over the videos seen), num_videos, num_sen, num_words, avg_sen_len,
+        num_empty, num_copied, vocab_size."""
+        v = [float(x) for x in self.acc.cpu()]
+        bits = self.vocab_bits.cpu().numpy().view("uint32")
+        nv = int(v[8])
+        res = {k: (v[i] / nv if nv else 0.0) for i, k in enumerate(self.FIELDS)}
+        num_sen, num_words = int(v[9]), int(v[10])
+        res.update(num_videos=nv, num_sen=num_sen, num_words=num_words, avg_sen_len=(num_words / num_sen) if num_sen else 0.0,
+                   num_empty=int(v[11]), num_copied=int(v[12]), vocab_size=int(sum(bin(int(x)).count("1") for x in bits[bits != 0])))
+        return res

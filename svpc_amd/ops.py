@@ -2821,3 +2821,128 @@ def sample_seed(src, word, used):
     _need_gpu(src)
     _lib.call("sample_seed", _p(src), _p(word), _p(used), _stream())
     return used
+
+
+CAPTION_LT_MAX = 64             # a caption row: one lane per position
+CAPTION_VIDEO_WORDS = 4096      # positions (S_b · Lt) of one video's captions: the words live in the workgroup's LDS
+CAPTION_COUNT_COLS = 12         # total_1..4, distinct_1..4, n_sen, n_words, n_empty, n_copied
+_NO_ID = -(1 << 31)             # "no such id" for the punctuation rule
+
+
+def check_caption_metrics(lt, ids_dtype=None, steps=None, k=None, row=None, period_id=None, comma_id=None):
+    """Host checks of the caption clean-up / counters (ValueError): ``lt`` ≤ 64 positions per row; ids int32 or int64; every video's
+    ``steps[b]`` · lt ≤ 4096 positions; ``row`` inside the ``k`` rows per sentence of a 3-D result (None or 0 for a 2-D one); the two
+    punctuation ids different.  → (row index, period, comma) as the kernels take them."""
+    if not 1 <= int(lt) <= CAPTION_LT_MAX:
+        raise ValueError("caption rows hold 1..%d positions, got Lt = %d" % (CAPTION_LT_MAX, lt))
+    if ids_dtype is not None and ids_dtype not in (torch.int32, torch.int64):
+        raise ValueError("caption ids must be int32 or int64, got %s" % (ids_dtype,))
+    for s in steps or ():
+        if int(s) < 0 or int(s) * int(lt) > CAPTION_VIDEO_WORDS:
+            raise ValueError("a video's captions hold at most %d positions (S_b · Lt), got %d · %d" % (CAPTION_VIDEO_WORDS, s, lt))
+    if isinstance(row, bool) or (row is not None and not isinstance(row, numbers.Integral)):
+        raise ValueError("row must be an integer, got %r" % (row,))
+    r = 0 if row is None else int(row)
+    if not 0 <= r < (1 if k is None else int(k)):
+        raise ValueError("row %d outside the %d row(s) per sentence" % (r, 1 if k is None else int(k)))
+    for name, v in (("period_id", period_id), ("comma_id", comma_id)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= int(v) < (1 << 31)):
+            raise ValueError("%s must be None or a token id, got %r" % (name, v))
+    if period_id is not None and period_id == comma_id:
+        raise ValueError("period_id and comma_id must differ, both are %d" % period_id)
+    return r, (_NO_ID if period_id is None else int(period_id)), (_NO_ID if comma_id is None else int(comma_id))
+
+
+def clean_captions(ids, pad, eos, ignore=-1, remove_dup=True, row=None):
+    """The captions the reference submits, from decoded ids (svpc_caption_clean): ``ids`` (T, Lt) or (T, K, Lt) int64 / int32 (``row``
+    picks one of the K rows per sentence, default 0) → (words (T, Lt) int32: the ids without ``pad`` / ``ignore``, without the first of
+    those, up to the first ``eos``, runs collapsed when ``remove_dup`` — left-aligned, ``pad``-filled; len (T,) int32)."""
+    if ids.dim() not in (2, 3):
+        raise ValueError("clean_captions: ids must be (T, Lt) or (T, K, Lt), got %s" % (tuple(ids.shape),))
+    lt = ids.shape[-1]
+    k = ids.shape[1] if ids.dim() == 3 else None
+    r, _, _ = check_caption_metrics(lt, ids.dtype, k=k, row=row)
+    _need_gpu(ids)
+    ids = _c(ids)
+    T = ids.shape[0]
+    words = torch.empty(T, lt, dtype=torch.int32, device=ids.device)
+    ln = torch.empty(T, dtype=torch.int32, device=ids.device)
+    _lib.call("caption_clean", _p(ids), 1 if ids.dtype == torch.int64 else 0, lt, 1 if k is None else int(k), r, T, lt, int(pad), int(eos),
+              int(ignore), 1 if remove_dup else 0, _p(words), _p(ln), _stream())
+    return words, ln
+
+
+def caption_ngram_counts(words, length, vid_off, V, period_id=None, comma_id=None, vocab_bits=None, steps=None):
+    """Per-video n-gram counts of clean captions (svpc_caption_ngram_counts): ``words`` (T, Lt) / ``length`` (T,) int32 as
+    ``clean_captions`` returns them, ``vid_off`` (N + 1,) int32 device tensor (or a host list, uploaded) of the videos' first rows →
+    counts (N, 12) int32: total_1..4, distinct_1..4, n_sen, n_words, n_empty, n_copied.  ``vocab_bits``: an int32 device bitmap of
+    ≥ ⌈V / 32⌉ words that collects the ids < V seen.  ``steps``: the videos' row counts when the caller knows them (a device ``vid_off``
+    is not read back to check the 4096-position cap)."""
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("caption_ngram_counts: words must be contiguous int32 (T, Lt)")
+    T, lt = words.shape
+    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
+        raise ValueError("caption_ngram_counts: len must be contiguous int32 (T,)")
+    if not torch.is_tensor(vid_off):
+        off = [int(v) for v in vid_off]
+        if steps is None:
+            steps = [b - a for a, b in zip(off[:-1], off[1:])]
+        if not off or off[0] != 0 or off[-1] != T:
+            raise ValueError("caption_ngram_counts: vid_off must run from 0 to T = %d" % T)
+    elif vid_off.dtype != torch.int32 or vid_off.dim() != 1 or vid_off.shape[0] < 1 or not vid_off.is_contiguous():
+        raise ValueError("caption_ngram_counts: vid_off must be a contiguous int32 (N + 1,) tensor")
+    _, period, comma = check_caption_metrics(lt, steps=steps, period_id=period_id, comma_id=comma_id)
+    if steps is not None and sum(int(s) for s in steps) != T:
+        raise ValueError("caption_ngram_counts: the videos' rows must add up to T = %d" % T)
+    if not 0 <= int(V) < (1 << 31):
+        raise ValueError("caption_ngram_counts: vocabulary size must be >= 0, got %r" % (V,))
+    if vocab_bits is not None and (vocab_bits.dtype != torch.int32 or not vocab_bits.is_contiguous() or vocab_bits.numel() * 32 < V
+                                   or vocab_bits.device != words.device):
+        raise ValueError("caption_ngram_counts: vocab_bits must be a contiguous int32 bitmap of >= V bits on the words' device")
+    _need_gpu(words)
+    if not torch.is_tensor(vid_off):
+        vid_off = torch.tensor(off, dtype=torch.int32, device=words.device)
+    N = vid_off.shape[0] - 1
+    counts = torch.empty(N, CAPTION_COUNT_COLS, dtype=torch.int32, device=words.device)
+    _lib.call("caption_ngram_counts", _p(words), _p(length), _p(vid_off), N, lt, period, comma, int(V), _p(counts), _p(vocab_bits), _stream())
+    return counts
+
+
+def decode_metric_accum(counts, acc):
+    """acc (13,) float64 += Σ over the rows of ``counts`` of (re_1..4, div_1..4, 1, n_sen, n_words, n_empty, n_copied) —
+    svpc_decode_metric_accum (fixed summation order)."""
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != CAPTION_COUNT_COLS or not counts.is_contiguous():
+        raise ValueError("decode_metric_accum: counts must be contiguous int32 (N, %d)" % CAPTION_COUNT_COLS)
+    if acc.dtype != torch.float64 or acc.numel() != 13 or not acc.is_contiguous() or acc.device != counts.device:
+        raise ValueError("decode_metric_accum: acc must be a contiguous float64 (13,) tensor on the counts' device")
+    _need_gpu(counts)
+    _lib.call("decode_metric_accum", _p(counts), counts.shape[0], _p(acc), _stream())
+    return acc
+
+
+def stack_captions(dec_seq_list):
+    """A decode's per-video id tensors ((S_b, Lt) or (S_b, K, Lt)) as one (T, …) tensor and the S_b: zero-copy when they are consecutive
+    views of one buffer (what the translator returns; ``model._stacked``'s test), else one ``torch.cat``."""
+    if not len(dec_seq_list):
+        raise ValueError("no captions: an empty list of videos")
+    t0 = dec_seq_list[0]
+    steps = [int(t.shape[0]) for t in dec_seq_list]
+    if any(t.dim() != t0.dim() or t.shape[1:] != t0.shape[1:] or t.dtype != t0.dtype or t.device != t0.device for t in dec_seq_list):
+        raise ValueError("the videos' id tensors must agree in dtype, device and all dimensions but the first")
+    if t0.dim() not in (2, 3):
+        raise ValueError("per-video ids must be (S_b, Lt) or (S_b, K, Lt), got %s" % (tuple(t0.shape),))
+    if len(dec_seq_list) == 1:
+        return _c(t0), steps
+    per = t0[0].numel() * t0.element_size() if steps[0] else 0
+    ptr, ok = t0.data_ptr(), per > 0
+    for t, s in zip(dec_seq_list, steps):
+        ok = ok and t.is_contiguous() and t.data_ptr() == ptr
+        ptr += s * per
+    root = t0._base
+    if ok and root is not None and root.is_contiguous() and root.dtype == t0.dtype:
+        start = (t0.data_ptr() - root.data_ptr()) // t0.element_size()
+        n = sum(steps) * t0[0].numel()
+        flat = root.reshape(-1)
+        if 0 <= start and start + n <= flat.numel():
+            return flat[start:start + n].view(sum(steps), *t0.shape[1:]), steps
+    return torch.cat(list(dec_seq_list)), steps

@@ -98,6 +98,12 @@ and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that t
 - every argument is checked on the host before any device work: ValueError for R, τ (finite > 0), k (≥ −1), q ([0, 1]), m (0 … Lt − 1),
   the seed, and rows wider than 4096 columns; TypeError for an unknown keyword; ``incremental=False`` raises NotImplementedError.
   Each setting (R, τ, k, q, m) has its own prepared plan and captured graph; the seed is a captured input.
+
+**Captions from ids** (the reference's host tail, src/translate.py:81-83): ``Translator.clean_captions(dec_seq_list, row=0,
+remove_dup=True)`` turns any of the results above into the clean captions on the device (the ids without PAD / IGNORE, without the first
+of those, up to the first EOS, runs of one word collapsed — ``convert_ids_to_sentence`` then ``remove_dup``), and
+``ids_to_sentences(clean, lens, idx2word, oov_word_dict)`` builds the strings on the host.  ``svpc_amd.metrics.DecodeMetrics`` counts
+the reference's repetition / diversity numbers from the same ids.  ``translate_batch*`` themselves do not change.
 """
 from __future__ import annotations
 
@@ -108,7 +114,18 @@ from . import ops
 from .model import BatchPlan, _Ctx
 from .ops import check_beam_controls, check_sampling, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
 from .ops_common import ACT_RELU, BulkUpload, Idx, SeqInfo
-from .synthetic import BOS, EOS, PAD, UNK
+from .synthetic import BOS, EOS, IGNORE, PAD, UNK
+
+
+def ids_to_sentences(clean, lens, idx2word, oov_word_dict):
+    """The strings of one video's clean captions (host): ``clean`` (S_b, Lt) ids and ``lens`` (S_b,) as ``Translator.clean_captions``
+    returns them (tensors, arrays or lists), ``idx2word`` id → word, ``oov_word_dict`` word → extended id of the video's copied words →
+    a list of S_b sentences, words joined by one blank — the reference's ``remove_dup(convert_ids_to_sentence(ids, oov_word_dict))``
+    (src/translate.py:82-83) when ``clean`` was made with ``remove_dup=True``."""
+    rows = clean.tolist() if hasattr(clean, "tolist") else [list(r) for r in clean]
+    ns = lens.tolist() if hasattr(lens, "tolist") else list(lens)
+    oov = {int(v): k for k, v in (oov_word_dict or {}).items()}
+    return [" ".join(idx2word[w] if w in idx2word else oov[w] for w in row[:int(n)]) for row, n in zip(rows, ns)]
 
 
 class Translator(object):
@@ -231,6 +248,21 @@ class Translator(object):
         key = ("sample", s["num_samples"], s["random_sampling_temp"], s["random_sampling_topk"], s["random_sampling_topp"], s["min_length"])
         return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
                                ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=s["num_samples"], sample=(key, s["seed"]))
+
+    def clean_captions(self, dec_seq_list, row=0, remove_dup=True):
+        """The captions the reference submits, on the device (``ops.clean_captions``): ``dec_seq_list`` as any
+        ``translate_batch*`` returns it (per video (S_b, Lt), or (S_b, K, Lt) with ``row`` picking one of the K) →
+        (clean_list, len_list): per video (S_b, Lt) int64 clean ids (PAD-filled) and (S_b,) int64 lengths, views of one buffer each.
+        One launch for the batch when the list is what the translator returned; no host synchronisation."""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, remove_dup, row=row)
+        words, ln = words.to(torch.int64), ln.to(torch.int64)
+        clean_list, len_list, o = [], [], 0
+        for s in steps:
+            clean_list.append(words[o:o + s])
+            len_list.append(ln[o:o + s])
+            o += s
+        return clean_list, len_list
 
     def _translate_beam(self, model_inputs, B, ctl, key, n_best):
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
