@@ -559,6 +559,25 @@ int svpc_caption_ngram_counts(const int* words, const int* len, const int* vid_o
 /* acc[0..12] += Σ_b (re_1..4, div_1..4, 1, n_sen, n_words, n_empty, n_copied) over the n_vid rows of counts, re_n = (total_n − distinct_n) /
  * total_n (0 when total_n = 0), div_n = distinct_n / total_1 (0 when total_1 = 0); fp64, summed in a fixed order (deterministic). */
 int svpc_decode_metric_accum(const int* counts, int n_vid, double* acc, svpc_stream_t stream);
+/* ---- ingredient-prediction recall / precision / F1 of clean captions (src/calculate_ingredient_f1.py:6-59), on the device.  The
+ *      reference's string rule (`ingredient in sentence`, then `word in all_ingredient_dict`) is carried by bit tables the host compiles
+ *      (svpc_amd/ingredients.py): pred (n_pred, pred_ld) — row p, bit i: vocabulary word i satisfies predicate p (contains / ends with /
+ *      equals / starts with a string); a_bits — vocabulary words in the global ingredient set.  words (n_rows, lt) / len as
+ *      svpc_caption_clean writes them; vid_off (n_vid + 1) first rows of the videos; row_vs (n_rows, 2) = (video, step) of every row.
+ *      vid (n_vid, 8) = {ing0, E <= 64, X <= 128 copied words, eq0, n_eq, gt0, n_gt, 0}: listed ingredient e of the video owns the pattern
+ *      tokens ing_tok[ing0 + e] … ing_tok[ing0 + e + 1] − 1; token j = predicate row tok_row[j] for ids < vocab and the 128 bits
+ *      tok_oov[4 j …] for the copied ids vocab … vocab + X − 1.  Ingredient e is mentioned when its tokens hold at consecutive positions.
+ *      Extra words: positions whose id is none of eq_ids[eq0 … eq0 + n_eq − 1] (ids that spell a whole listed ingredient) and is in the
+ *      set (a_bits, or the video's 128 bits oov_a[4 b …]).  Generated step s < n_gt is compared with ground-truth step g = gt0 + s:
+ *      gt_mask (2 words per step, low first) its listed ingredients, gx_ids[gx_off[g] … gx_off[g + 1] − 1] the ids of its extra words,
+ *      gt_len[g] the length of its list.  Out: masks (n_rows) int64, extra (n_rows) extra words, row_counts (n_rows, 3) = correct, generated
+ *      list length, ground-truth list length (zeros for a step without ground truth), vid_counts (n_vid, 3) their sums per video;
+ *      acc[0..2] (or NULL) += the three totals, 64-bit integer atomics: any sequence of calls gives the same bits. */
+int svpc_caption_ingredients(const int* words, const int* len, int n_rows, int lt, const int* vid_off, const int* row_vs, int n_vid,
+                             const unsigned* pred, int pred_ld, int n_pred, const unsigned* a_bits, int vocab, const int* vid,
+                             const int* ing_tok, const int* tok_row, const unsigned* tok_oov, const int* eq_ids, const unsigned* oov_a,
+                             const unsigned* gt_mask, const int* gt_len, const int* gx_off, const int* gx_ids, long long* masks, int* extra,
+                             int* row_counts, int* vid_counts, unsigned long long* acc, svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

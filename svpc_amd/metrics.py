@@ -8,7 +8,8 @@ updated by two small kernels per video; ``result()`` is the only host read-back.
 ``DecodeMetrics`` is the evaluation-side counterpart: the captions the reference submits and its repetition / diversity numbers
 (src/translate.py:27-42 and :81-83, recursive_caption_dataset.py:472-500, densevid_eval/evaluateRepetition.py,
 evaluateCaptionsDiversity.py:219-282, get_caption_stat.py) from the translator's id matrices, three launches per batch and no host
-synchronisation until ``result()``.
+synchronisation until ``result()``.  ``IngredientF1`` adds the ingredient-prediction recall / precision / F1 of
+src/calculate_ingredient_f1.py from the same clean captions.
 """
 from __future__ import annotations
 
@@ -107,12 +108,13 @@ class DecodeMetrics:
         self.acc = torch.zeros(13, dtype=torch.float64, device=self.device)
         self.vocab_bits = torch.zeros((self.V + 31) // 32, dtype=torch.int32, device=self.device)
         self.last_counts = None
+        self.last_clean = None              # the last update's (words, len): IngredientF1.update(..., clean=) reuses it
         self._offs = {}
 
     def reset(self):
         self.acc.zero_()
         self.vocab_bits.zero_()
-        self.last_counts = None
+        self.last_counts = self.last_clean = None
 
     def _vid_off(self, steps, dev):
         """the (N + 1,) int32 table of the videos' first rows: uploaded once per (S_b) structure"""
@@ -137,7 +139,7 @@ class DecodeMetrics:
         counts = ops.caption_ngram_counts(words, ln, self._vid_off(steps, ids.device), self.V, self.period_id, self.comma_id,
                                           vocab_bits=self.vocab_bits, steps=steps)
         ops.decode_metric_accum(counts, self.acc)
-        self.last_counts = counts
+        self.last_counts, self.last_clean = counts, (words, ln)
         return counts
 
     def result(self):
@@ -150,4 +152,56 @@ class DecodeMetrics:
         num_sen, num_words = int(v[9]), int(v[10])
         res.update(num_videos=nv, num_sen=num_sen, num_words=num_words, avg_sen_len=(num_words / num_sen) if num_sen else 0.0,
                    num_empty=int(v[11]), num_copied=int(v[12]), vocab_size=int(sum(bin(int(x)).count("1") for x in bits[bits != 0])))
+        return res
+
+
+class IngredientF1:
+    """Running ingredient-prediction recall / precision / F1 (src/calculate_ingredient_f1.py) of an evaluation epoch, kept on the device.
+
+    ``update(dec_seq_list, plan, row=0, clean=None)`` takes what any ``translate_batch*`` returns and ``lexicon.plan(videos)`` of the same
+    videos (with ``gt_sentences``); ``clean=(words, len)`` reuses a clean-up already made with run collapse on (``ops.clean_captions`` of
+    the same rows, or ``DecodeMetrics.last_clean`` after its ``update`` of the same result and row), otherwise one ``ops.clean_captions``
+    call is made.  Then ``ops.caption_ingredients``:
+    two launches, integer atomics into ``acc`` = [correct, precision total, recall total] (int64), so a given sequence of updates always
+    gives the same bits; nothing uploaded for a recurring batch, so ``update`` can be captured.  ``result()`` is the only read-back.
+    ``last_masks`` / ``last_extra``: the last update's (T,) int64 masks and int32 extra-word counts; ``last_counts``: its (N, 3) int32
+    per-video (correct, len(generated lists), len(ground-truth lists))."""
+
+    def __init__(self, lexicon):
+        self.lexicon = lexicon
+        self.device = torch.device(lexicon.device)
+        if self.device.type != "cuda":
+            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.acc = torch.zeros(3, dtype=torch.int64, device=self.device)
+        self.last_masks = self.last_extra = self.last_counts = None
+
+    def reset(self):
+        self.acc.zero_()
+        self.last_masks = self.last_extra = self.last_counts = None
+
+    def update(self, dec_seq_list, plan, row=0, clean=None):
+        if plan.lexicon is not self.lexicon:
+            raise ValueError("the plan was made by another lexicon")
+        if not plan.has_gt:
+            raise ValueError("IngredientF1 needs the ground-truth sentences of every video (gt_sentences in lexicon.plan)")
+        ids, steps = ops.stack_captions(dec_seq_list)
+        lt = ids.shape[-1]
+        ops.check_caption_metrics(lt, ids.dtype, steps=steps, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
+        if not ids.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
+        if clean is None:
+            clean = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        words, ln = clean
+        if tuple(words.shape) != (ids.shape[0], lt):
+            raise ValueError("clean=(words, len) must be the clean-up of these %d rows of %d positions" % (ids.shape[0], lt))
+        masks, extra, _, counts = ops.caption_ingredients(words, ln, plan, self.acc, steps=steps)
+        self.last_masks, self.last_extra, self.last_counts = masks, extra, counts
+        return counts
+
+    def result(self):
+        """The single host read-back → recall, precision, f1 (``compute_total_f1``: 0 where the reference would divide by zero),
+        n_correct, n_recall, n_precision."""
+        c, p, r = (int(x) for x in self.acc.cpu())
+        res = compute_total_f1(c, r, p)
+        res.update(n_correct=c, n_recall=r, n_precision=p)
         return res

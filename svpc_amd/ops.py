@@ -2946,3 +2946,40 @@ def stack_captions(dec_seq_list):
         if 0 <= start and start + n <= flat.numel():
             return flat[start:start + n].view(sum(steps), *t0.shape[1:]), steps
     return torch.cat(list(dec_seq_list)), steps
+
+
+def caption_ingredients(words, length, plan, acc=None, steps=None):
+    """Which ingredients clean captions mention, and the ingredient-F1 counts against the plan's ground truth (svpc_caption_ingredients;
+    DESIGN §11.5): ``words`` (T, Lt) / ``length`` (T,) int32 as ``clean_captions`` returns them (run collapse on), ``plan`` an
+    ``ingredients.IngredientPlan``, ``steps`` the videos' row counts (default: their ground-truth step counts), ``acc`` a contiguous int64
+    (3,) device tensor (correct, precision total = Σ len(generated list), recall total = Σ len(ground-truth list); None: nothing
+    accumulated) →
+    (masks (T,) int64: bit e = listed ingredient e of the row's video is mentioned; extra (T,) int32 extra words;
+    row_counts (T, 3) int32 = correct, len(generated list), len(ground-truth list), zeros for a row without a ground-truth step;
+    vid_counts (N, 3) int32 their sums per video).  Two launches, nothing uploaded for a recurring (S_b) structure."""
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("caption_ingredients: words must be contiguous int32 (T, Lt)")
+    T, lt = words.shape
+    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
+        raise ValueError("caption_ingredients: len must be contiguous int32 (T,)")
+    check_caption_metrics(lt)
+    steps = plan.default_steps() if steps is None else [int(s) for s in steps]
+    if len(steps) != plan.n_vid or sum(steps) != T:
+        raise ValueError("caption_ingredients: the plan's %d video(s) with rows %r do not add up to T = %d" % (plan.n_vid, steps, T))
+    if plan.buf.device != words.device:
+        raise ValueError("caption_ingredients: the plan lives on %s, the captions on %s" % (plan.buf.device, words.device))
+    if acc is not None and (acc.dtype != torch.int64 or acc.numel() != 3 or not acc.is_contiguous() or acc.device != words.device):
+        raise ValueError("caption_ingredients: acc must be a contiguous int64 (3,) tensor on the captions' device")
+    _need_gpu(words)
+    rows = plan.rows(steps)
+    lex, N = plan.lexicon, plan.n_vid
+    dev = words.device
+    masks = torch.empty(T, dtype=torch.int64, device=dev)
+    extra = torch.empty(T, dtype=torch.int32, device=dev)
+    row_counts = torch.empty(T, 3, dtype=torch.int32, device=dev)
+    vid_counts = torch.empty(N, 3, dtype=torch.int32, device=dev)
+    _lib.call("caption_ingredients", _p(words), _p(length), T, lt, rows.data_ptr(), rows.data_ptr() + 4 * (N + 1), N,
+              _p(lex.table), lex.W, lex.n_rows, _p(lex.a_bits), lex.V, plan.ptr("vid"), plan.ptr("ing_tok"), plan.ptr("tok_row"),
+              plan.ptr("tok_oov"), plan.ptr("eq_ids"), plan.ptr("oov_a"), plan.ptr("gt_mask"), plan.ptr("gt_len"), plan.ptr("gx_off"),
+              plan.ptr("gx_ids"), _p(masks), _p(extra), _p(row_counts), _p(vid_counts), _p(acc), _stream())
+    return masks, extra, row_counts, vid_counts

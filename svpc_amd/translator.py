@@ -103,7 +103,9 @@ and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that t
 remove_dup=True)`` turns any of the results above into the clean captions on the device (the ids without PAD / IGNORE, without the first
 of those, up to the first EOS, runs of one word collapsed — ``convert_ids_to_sentence`` then ``remove_dup``), and
 ``ids_to_sentences(clean, lens, idx2word, oov_word_dict)`` builds the strings on the host.  ``svpc_amd.metrics.DecodeMetrics`` counts
-the reference's repetition / diversity numbers from the same ids.  ``translate_batch*`` themselves do not change.
+the reference's repetition / diversity numbers from the same ids.  ``Translator.caption_ingredients(dec_seq_list, plan,
+row=0)`` tells which of a recipe's ingredients each caption mentions (the rule of src/calculate_ingredient_f1.py, on the device;
+``svpc_amd.metrics.IngredientF1`` accumulates its recall / precision / F1 — DESIGN §11.5).  ``translate_batch*`` themselves do not change.
 """
 from __future__ import annotations
 
@@ -263,6 +265,22 @@ class Translator(object):
             len_list.append(ln[o:o + s])
             o += s
         return clean_list, len_list
+
+    def caption_ingredients(self, dec_seq_list, plan, row=0):
+        """Which ingredients each decoded caption mentions (``ops.caption_ingredients``): ``dec_seq_list`` as any
+        ``translate_batch*`` returns it, ``plan`` = ``IngredientLexicon.plan(videos)`` of the same videos → (mask_list, extra_list): per
+        video (S_b,) int64 masks (bit e: listed ingredient e is mentioned; ``ingredients.masks_to_names`` gives the names) and (S_b,)
+        int64 counts of the other known ingredient words, views of one buffer each.  No host synchronisation."""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        masks, extra, _, _ = ops.caption_ingredients(words, ln, plan, None, steps=steps)
+        extra = extra.to(torch.int64)
+        mask_list, extra_list, o = [], [], 0
+        for s in steps:
+            mask_list.append(masks[o:o + s])
+            extra_list.append(extra[o:o + s])
+            o += s
+        return mask_list, extra_list
 
     def _translate_beam(self, model_inputs, B, ctl, key, n_best):
         (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
