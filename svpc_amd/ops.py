@@ -2530,6 +2530,27 @@ LENGTH_PENALTIES = ("none", "avg", "wu")
 BLOCK_SCOPES = ("sentence", "paragraph")
 
 
+def _as_int(name, v):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise ValueError("%s must be an integer, got %r" % (name, v))
+    return int(v)
+
+
+def _row_vec(t, R, dtype, device=None):
+    """``t`` is an (R,) contiguous tensor of ``dtype`` (on ``device``, when given)"""
+    return t.dtype == dtype and t.shape == (R,) and t.is_contiguous() and (device is None or t.device == device)
+
+
+def _id_rows(m, R, lt, device=None):
+    """``m`` is an (R, lt) contiguous int32 matrix (on ``device``, when given)"""
+    return m.dtype == torch.int32 and tuple(m.shape) == (R, lt) and m.is_contiguous() and (device is None or m.device == device)
+
+
+def _lp_table(lp, lt, device=None):
+    """``lp`` is a contiguous float64 table of at least ``lt`` entries (on ``device``, when given)"""
+    return lp.dtype == torch.float64 and lp.dim() == 1 and lp.shape[0] >= lt and lp.is_contiguous() and (device is None or lp.device == device)
+
+
 def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_tokens=(), min_length=0, length_penalty_name="none",
                         length_penalty_alpha=0.0, n_best=None, block_ngram_scope="sentence", max_cols=None):
     """The decoding controls of a beam decode over Lt = ``lt`` positions and ``vocab`` text ids, checked on the host (ValueError) and
@@ -2537,19 +2558,15 @@ def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_to
     block_ngram_scope [, n_best]).  n: 0 … Lt − 1 (and Lt ≤ 64 when n > 0); m: 0 … Lt − 1; exclusion ids in [0, vocab); alpha finite ≥ 0;
     n_best 1 … beam; scope ``sentence`` or ``paragraph`` (needs n > 0 and score rows of at most SAMPLE_COLS_MAX columns: ``max_cols``, the
     widest row V + X, default ``vocab``)."""
-    def as_int(name, v):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise ValueError("%s must be an integer, got %r" % (name, v))
-        return int(v)
-    n = as_int("block_ngram_repeat", block_ngram_repeat)
-    m = as_int("min_length", min_length)
+    n = _as_int("block_ngram_repeat", block_ngram_repeat)
+    m = _as_int("min_length", min_length)
     if not 0 <= n <= lt - 1:
         raise ValueError("block_ngram_repeat must be 0..%d (Lt - 1), got %d" % (lt - 1, n))
     if n > 0 and lt > 64:
         raise ValueError("block_ngram_repeat needs Lt <= 64 (one wave holds a hypothesis's ids), Lt = %d" % lt)
     if not 0 <= m <= lt - 1:
         raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (lt - 1, m))
-    excl = tuple(sorted({as_int("exclusion_tokens", e) for e in (exclusion_tokens or ())}))
+    excl = tuple(sorted({_as_int("exclusion_tokens", e) for e in (exclusion_tokens or ())}))
     for e in excl:
         if not 0 <= e < vocab:
             raise ValueError("exclusion_tokens must be text ids in [0, %d), got %d" % (vocab, e))
@@ -2572,7 +2589,7 @@ def check_beam_controls(lt, vocab, beam=None, block_ngram_repeat=0, exclusion_to
     out = dict(block_ngram_repeat=n, exclusion_tokens=excl, min_length=m, length_penalty_name=name, length_penalty_alpha=alpha,
                block_ngram_scope=scope)
     if n_best is not None:
-        k = as_int("n_best", n_best)
+        k = _as_int("n_best", n_best)
         if beam is None or not 1 <= k <= beam:
             raise ValueError("n_best must be 1..%s (the beam width), got %d" % (beam, k))
         out["n_best"] = k
@@ -2623,12 +2640,11 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
     R = cum.shape[0]
     if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
         raise ValueError("beam_step: scores must be fp32 (T·beam, C) rows with unit column stride")
-    if not (cum.dtype == torch.float32 and finished.dtype == torch.int32 and finished.shape == cum.shape and cum.is_contiguous()
-            and finished.is_contiguous()):
+    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
         raise ValueError("beam_step: cum fp32 and finished int32, both contiguous (T·beam,)")
     lt = toks_in[0].shape[1]
     for m in tuple(toks_in) + tuple(toks_out):
-        if m.dtype != torch.int32 or not m.is_contiguous() or tuple(m.shape) != (R, lt) or m.device != scores.device:
+        if not _id_rows(m, R, lt, scores.device):
             raise ValueError("beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
     if not 0 <= pos < lt - 1 or slot_rows < lt:
         raise ValueError("beam_step: position %d outside the %d-column tables" % (pos, lt))
@@ -2638,8 +2654,7 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
         desc = as_idx(desc)
         if int(block_ngram_repeat) < 1 or lt > 64:
             raise ValueError("beam_step: paragraph scope needs block_ngram_repeat >= 1 and Lt <= 64")
-        if (table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != lt or not table.is_contiguous()
-                or table.device != scores.device):
+        if table.dim() != 2 or not _id_rows(table, table.shape[0], lt, scores.device):
             raise ValueError("beam_step: the history must be a contiguous int32 (rows, Lt) matrix on the scores' device")
         d = desc.host
         if len(d) != 2 * (R // beam) or any(c < 0 or f < 0 or f + c > table.shape[0] for f, c in zip(d[0::2], d[1::2])):
@@ -2652,11 +2667,9 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
             raise ValueError("beam_step: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
         if block_ngram_repeat and lt > 64:
             raise ValueError("beam_step: block_ngram_repeat needs Lt <= 64")
-        if length is not None and (length.dtype != torch.int32 or length.shape != (R,) or not length.is_contiguous()
-                                   or length.device != scores.device):
+        if length is not None and not _row_vec(length, R, torch.int32, scores.device):
             raise ValueError("beam_step: length must be contiguous int32 (T·beam,) on the scores' device")
-        if lp is not None and (length is None or lp.dtype != torch.float64 or lp.dim() != 1 or lp.shape[0] < lt or not lp.is_contiguous()
-                               or lp.device != scores.device):
+        if lp is not None and (length is None or not _lp_table(lp, lt, scores.device)):
             raise ValueError("beam_step: lp must be a contiguous float64 table of >= Lt entries on the scores' device, with length")
         if exclusion is not None:
             bits, vocab = exclusion
@@ -2668,37 +2681,35 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
     parent = torch.empty(R, dtype=torch.int32, device=dev)
     nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
     nxt = torch.empty(R, dtype=torch.int32, device=dev)
-    if history is not None:
-        bits, vocab = exclusion if exclusion is not None else (None, 0)
-        _lib.call("beam_step_para", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam,
-                  int(beam), int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
-                  _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
-                  int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _p(table), _p(desc.dev(dev)), int(bos),
-                  _stream())
-        return parent, nxt_ext, nxt
+    args = [_p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
+            1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
+            _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt)]
+    name = "beam_step"
     if ctl:
         bits, vocab = exclusion if exclusion is not None else (None, 0)
-        _lib.call("beam_step_ctl", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
-                  int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
-                  _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
-                  int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _stream())
-        return parent, nxt_ext, nxt
-    _lib.call("beam_step", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
-              1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
-              _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt), _stream())
+        name, args = "beam_step_ctl", args + [int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length)]
+    if history is not None:
+        name, args = "beam_step_para", args + [_p(table), _p(desc.dev(dev)), int(bos)]
+    _lib.call(name, *args, _stream())
     return parent, nxt_ext, nxt
+
+
+def _check_finalize(cum, ext, beam, n_best=1):
+    """the arguments the two final picks share → (T, Lt)"""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_finalize: beam width must be 1..%d" % BEAM_MAX)
+    if not 1 <= n_best <= beam:
+        raise ValueError("beam_finalize: n_best must be 1..%d, got %r" % (beam, n_best))
+    R, lt = ext.shape
+    if R % beam or not _row_vec(cum, R, torch.float32) or not _id_rows(ext, R, lt):
+        raise ValueError("beam_finalize: cum fp32 (T·beam,) and ext int32 (T·beam, Lt), contiguous")
+    return R // beam, lt
 
 
 def beam_finalize(cum, ext, beam):
     """→ (ids (T, Lt) int32, score (T,) fp32): per sentence the hypothesis of highest ``cum`` (ties: lowest index) — svpc_beam_finalize."""
-    if not 1 <= beam <= BEAM_MAX:
-        raise ValueError("beam_finalize: beam width must be 1..%d" % BEAM_MAX)
-    R, lt = ext.shape
-    if (R % beam or cum.shape != (R,) or cum.dtype != torch.float32 or ext.dtype != torch.int32 or not ext.is_contiguous()
-            or not cum.is_contiguous()):
-        raise ValueError("beam_finalize: cum fp32 (T·beam,) and ext int32 (T·beam, Lt), contiguous")
+    T, lt = _check_finalize(cum, ext, beam)
     _need_gpu(ext)
-    T = R // beam
     ids = torch.empty(T, lt, dtype=torch.int32, device=ext.device)
     score = torch.empty(T, dtype=torch.float32, device=ext.device)
     _lib.call("beam_finalize", _p(cum), _p(ext), lt, T, int(beam), lt, _p(ids), _p(score), _stream())
@@ -2709,20 +2720,12 @@ def beam_finalize_nbest(cum, ext, beam, n_best, length=None, lp=None):
     """→ (ids (T, n_best, Lt) int32, score (T, n_best) fp32, len (T, n_best) int32): per sentence its ``n_best`` hypotheses in order of
     (double)cum / lp[len] (``lp`` None: cum), ties to the lower beam index — svpc_beam_finalize_nbest.  ``length`` (T·beam,) int32 (needed
     with ``lp``; None: len 0)."""
-    if not 1 <= beam <= BEAM_MAX:
-        raise ValueError("beam_finalize: beam width must be 1..%d" % BEAM_MAX)
-    if not 1 <= n_best <= beam:
-        raise ValueError("beam_finalize: n_best must be 1..%d, got %r" % (beam, n_best))
-    R, lt = ext.shape
-    if (R % beam or cum.shape != (R,) or cum.dtype != torch.float32 or ext.dtype != torch.int32 or not ext.is_contiguous()
-            or not cum.is_contiguous()):
-        raise ValueError("beam_finalize: cum fp32 (T·beam,) and ext int32 (T·beam, Lt), contiguous")
-    if length is not None and (length.dtype != torch.int32 or length.shape != (R,) or not length.is_contiguous()):
+    T, lt = _check_finalize(cum, ext, beam, n_best)
+    if length is not None and not _row_vec(length, T * beam, torch.int32):
         raise ValueError("beam_finalize: length must be contiguous int32 (T·beam,)")
-    if lp is not None and (length is None or lp.dtype != torch.float64 or lp.dim() != 1 or lp.shape[0] < lt or not lp.is_contiguous()):
+    if lp is not None and (length is None or not _lp_table(lp, lt)):
         raise ValueError("beam_finalize: lp must be a contiguous float64 table of >= Lt entries, with length")
     _need_gpu(ext)
-    T = R // beam
     ids = torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device)
     score = torch.empty(T, n_best, dtype=torch.float32, device=ext.device)
     ln = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
@@ -2740,11 +2743,7 @@ def check_sampling(lt, num_samples=1, random_sampling_temp=1.0, random_sampling_
     num_samples R (1 … BEAM_MAX), random_sampling_temp τ (finite > 0), random_sampling_topk k (0: off; OpenNMT's −1 is taken as 0),
     random_sampling_topp q (in [0, 1]; 0 and 1: off), min_length m (0 … Lt − 1), seed (None or an int in [0, 2⁶³))).  ``max_cols``: the
     widest score row C_r = V + X of the batch (≤ SAMPLE_COLS_MAX)."""
-    def as_int(name, v):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise ValueError("%s must be an integer, got %r" % (name, v))
-        return int(v)
-    R = as_int("num_samples", num_samples)
+    R = _as_int("num_samples", num_samples)
     if not 1 <= R <= BEAM_MAX:
         raise ValueError("num_samples must be 1..%d, got %d" % (BEAM_MAX, R))
     try:
@@ -2753,7 +2752,7 @@ def check_sampling(lt, num_samples=1, random_sampling_temp=1.0, random_sampling_
         raise ValueError("random_sampling_temp must be a number, got %r" % (random_sampling_temp,))
     if not math.isfinite(temp) or temp <= 0:
         raise ValueError("random_sampling_temp must be finite and > 0, got %r" % (random_sampling_temp,))
-    k = as_int("random_sampling_topk", random_sampling_topk)
+    k = _as_int("random_sampling_topk", random_sampling_topk)
     if k < -1:
         raise ValueError("random_sampling_topk must be >= -1 (0 or -1: the full distribution), got %d" % k)
     try:
@@ -2762,11 +2761,11 @@ def check_sampling(lt, num_samples=1, random_sampling_temp=1.0, random_sampling_
         raise ValueError("random_sampling_topp must be a number, got %r" % (random_sampling_topp,))
     if not 0.0 <= q <= 1.0:                       # (NaN fails too)
         raise ValueError("random_sampling_topp must be in [0, 1], got %r" % (random_sampling_topp,))
-    m = as_int("min_length", min_length)
+    m = _as_int("min_length", min_length)
     if not 0 <= m <= lt - 1:
         raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (lt - 1, m))
     if seed is not None:
-        seed = as_int("seed", seed)
+        seed = _as_int("seed", seed)
         if not 0 <= seed < 1 << 63:
             raise ValueError("seed must be None or an integer in [0, 2**63), got %d" % seed)
     if max_cols is not None and int(max_cols) > SAMPLE_COLS_MAX:
@@ -2786,11 +2785,11 @@ def sample_step(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished,
     if scores.dim() != 2 or scores.shape[0] != R or scores.stride(1) != 1 or scores.dtype != torch.float32:
         raise ValueError("sample_step: scores must be fp32 (T·R, C) rows with unit column stride")
     for t, dt in ((cum, torch.float32), (finished, torch.int32), (length, torch.int32)):
-        if t.dtype != dt or t.shape != (R,) or not t.is_contiguous() or t.device != scores.device:
+        if not _row_vec(t, R, dt, scores.device):
             raise ValueError("sample_step: cum fp32, finished and length int32, all contiguous (T·R,) on the scores' device")
     lt = text.shape[1]
     for m in (text, ext):
-        if m.dtype != torch.int32 or not m.is_contiguous() or tuple(m.shape) != (R, lt) or m.device != scores.device:
+        if not _id_rows(m, R, lt, scores.device):
             raise ValueError("sample_step: id matrices must be contiguous int32 (T·R, Lt) on the scores' device")
     if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
         raise ValueError("sample_step: seed must be a device int64 tensor")

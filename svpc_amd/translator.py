@@ -109,6 +109,8 @@ row=0)`` tells which of a recipe's ingredients each caption mentions (the rule o
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -128,6 +130,105 @@ def ids_to_sentences(clean, lens, idx2word, oov_word_dict):
     ns = lens.tolist() if hasattr(lens, "tolist") else list(lens)
     oov = {int(v): k for k, v in (oov_word_dict or {}).items()}
     return [" ".join(idx2word[w] if w in idx2word else oov[w] for w in row[:int(n)]) for row, n in zip(rows, ns)]
+
+
+GREEDY, BEAM, SAMPLE = "greedy", "beam", "sample"
+
+
+class Decode(object):
+    """What decode a call asks for: built by the public entry points, passed through ``_translate`` to ``_prepare`` and the device part.
+    ``kind``: GREEDY, BEAM or SAMPLE; ``width``: the rows per sentence (beam width B, samples R; greedy 1); ``controls`` / ``ctl_key``: the
+    checked decoding controls and their key (None: all off); ``sampling``: the checked (τ, k, q, m).  ``key`` is the decode's part of the
+    plan cache key.  Outside it: ``n_best`` — the rows per sentence the call returns (0: the chosen caption alone; it only slices the
+    result) — and ``seed``, this call's seed (a captured input)."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed")
+
+    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None):
+        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed = (
+            kind, width, controls, ctl_key, n_best, sampling, seed)
+
+    @property
+    def ranked(self):
+        """decoding controls and / or n-best: lengths tracked, all B final hypotheses sorted by their key"""
+        return self.kind == BEAM and (self.n_best > 0 or self.ctl_key is not None)
+
+    @property
+    def key(self):
+        return (self.kind, self.width, self.ctl_key, self.ranked, self.sampling)
+
+
+class DecodePlan(object):
+    """Everything of a decode that depends on the batch STRUCTURE and the ``Decode`` setting only (``Translator._prepare``): cached, and
+    the owner of the setting's captured graphs.  A field its mode does not use is None."""
+    __slots__ = ("key", "plan", "spans", "c_list", "T",       # the structure: BatchPlan, ingredient spans, columns per video, sentences
+                 "kind", "width", "ranked",                     # of the Decode
+                 "ptr_all", "x_all",                            # pointer plan and OOV counts, Lt rows per sentence (incremental=False)
+                 "ptr_hyp", "x_hyp",                            # the same, ``width`` rows per sentence: row t·width + h (incremental)
+                 "controls",                                    # ranked: ops.beam_step's keywords (device tables)
+                 "rounds", "rows_max",                          # paragraph scope: the round tables, the largest round's rows
+                 "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
+                 "seq_cross", "seq_self",                       # segmentations, built on first use
+                 "graphs")                                      # replay stream → (graph, captured inputs, outputs, signature)
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields.pop(k, None))
+        assert not fields, sorted(fields)
+        self.seq_cross, self.graphs = {}, {}
+
+
+class _DecoderSide(object):
+    """The decoder side of one incremental decode, built once after the encoder side: the memory K|V projection (one wide matrix for the
+    whole stack, or one per layer), the pointer bank and its projection, the text-embedding table.  The greedy, beam, sampling and
+    paragraph loops take their caches and rows from it and run every iteration through ``scores``."""
+
+    def __init__(self, model, cx, mem, bank, tab, T):
+        self.model, self.cx, self.bank, self.tab, self.T = model, cx, bank, tab, T
+        self.layers = model.decoder.layer
+        self.n_mem = mem.shape[0] // T
+        st = model.decoder.stacked_memory_kv()
+        self.stacked = st is not None          # one projection of the memory rows for the whole stack; each layer reads its columns
+        self.wide = [ops.linear(mem, st[0], st[1])] if st is not None else [layer.memory_kv(mem) for layer in self.layers]
+        self.proj = model.bank_projection(bank) if bank is not None else None
+
+    def caches(self, n_rows):
+        """the per-layer KV caches: one slot of Lt rows per hypothesis row"""
+        cfg = self.model.config
+        return [torch.zeros(n_rows * cfg.max_t_len, 2 * cfg.hidden_size, dtype=torch.float32, device=self.wide[0].device) for _ in self.layers]
+
+    def seq_cross(self, dp):
+        """row r of the T·width hypothesis rows over the memory rows of its sentence r // width"""
+        sq = dp.seq_cross.get(self.n_mem)
+        if sq is None:
+            W, n, R = dp.width, self.n_mem, dp.T * dp.width
+            sq = dp.seq_cross[n] = SeqInfo(list(range(R)), [1] * R, [(r // W) * n for r in range(R)], [n] * R, self.wide[0].device)
+        return sq
+
+    def rows(self, rd=None):
+        """(per-layer memory K|V, bank, bank projection) of the whole batch, or — row gathers — of the sentences of paragraph round ``rd``"""
+        wide, bank, proj = self.wide, self.bank, self.proj
+        if rd is not None:
+            dev = wide[0].device
+            mem_rows, sent = rd.mem_rows.dev(dev), rd.sent32.dev(dev)
+            wide = [ops.take_rows_f32(w, mem_rows) for w in wide]
+            bank = ops.take_rows_f32(bank.reshape(self.T, -1), sent).view(rd.n, *bank.shape[1:]) if bank is not None else None
+            proj = ops.take_rows_f32(proj.reshape(self.T, -1), sent).view(rd.n, *proj.shape[1:]) if proj is not None else None
+        return ops.split_cols(wide[0], len(self.layers)) if self.stacked else wide, bank, proj
+
+    def scores(self, rows, ptr, nxt, i, caches, seq_self, seq_cross, key_rows=None, group=1):
+        """one decoding iteration over hypothesis rows → their score rows: the text embedding of tokens ``nxt`` at position i (a row of the
+        per-checkpoint table: one gather instead of LayerNorm(300) → projection → LayerNorm + position encoding), the layers over each
+        row's ancestry ``key_rows`` in the KV caches (``group`` rows per sentence share its memory K|V; greedy: no table, group 1), then
+        the head — raw logits in ``video`` mode (the step score is their log_softmax; translator.py:159) — or the pointer-generator's
+        probabilities"""
+        model, cx = self.model, self.cx
+        mem_kv, bank, proj = rows
+        x = ops.take_rows(self.tab[i], nxt) if self.tab is not None else model.text_embeddings.run_at(nxt, i, cx)
+        for layer, cache, kv in zip(self.layers, caches, mem_kv):
+            x = layer.step(x, i, model.config.max_t_len, cache, kv, seq_self, seq_cross, cx, key_rows=key_rows, q_group=group)
+        if model.config.model_mode == "video":
+            return model.decoder_classifier.run(x, cx.eps)
+        return model._lm_probs(x, bank, ptr, cx, proj=proj)[0]
 
 
 class Translator(object):
@@ -199,21 +300,13 @@ class Translator(object):
         if self._controls(controls)[1] is not None:        # greedy with controls: the width-1 beam (B = 1 picks what greedy picks)
             dec, oov, _ = self.translate_batch_beam(model_inputs, 1, **controls)
             return dec, oov
-        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
-         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
-        return self.translate_batch_greedy(input_ids_list, video_features_list, input_masks_list, token_type_ids_list,
-                                           ingr_input_ids, ingr_masks, ingr_sep_masks, ingr_id_dict, oov_word_dict,
-                                           alignments, actions, batch_step_num, self.model)
+        return self.translate_batch_greedy(*model_inputs, self.model)
 
     @torch.no_grad()
     def translate_batch_beam(self, model_inputs, beam_size, **controls):
         """Beam search of width ``beam_size`` (module docstring) → (dec_seq_list, oov_word_dict, score_list): per video an (S_b, Lt)
         int64 id matrix, as greedy, and an (S_b,) fp32 tensor of the chosen hypotheses' summed step scores."""
-        B = int(beam_size)
-        if not 1 <= B <= ops.BEAM_MAX:
-            raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, beam_size))
-        if not self.incremental:
-            raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        B = self._beam_width(beam_size, beam_size)
         ctl, key = self._controls(controls)
         res, oov, scores, _ = self._translate_beam(model_inputs, B, ctl, key, 0)
         return res, oov, scores
@@ -223,13 +316,27 @@ class Translator(object):
         """The ``n_best`` best hypotheses of a width-``beam_size`` beam search (defaults ``opt.beam_size``, ``opt.n_best``; module
         docstring) → (dec_seq_list, oov_word_dict, score_list, length_list): per video ids (S_b, n_best, Lt) int64, cum (S_b, n_best)
         fp32 and len (S_b, n_best) int64, rows in final-key order."""
-        B = int(beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2))
-        if not 1 <= B <= ops.BEAM_MAX:
-            raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, beam_size))
-        if not self.incremental:
-            raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        B = self._beam_width(beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2), beam_size)
         ctl, key = self._controls(controls, beam=B, n_best=n_best if n_best is not None else getattr(self.opt, "n_best", 1))
         return self._translate_beam(model_inputs, B, ctl, key, ctl["n_best"])
+
+    def _beam_width(self, beam_size, given):
+        B = int(beam_size)
+        if not 1 <= B <= ops.BEAM_MAX:
+            raise ValueError("beam_size must be 1..%d, got %r" % (ops.BEAM_MAX, given))
+        if not self.incremental:
+            raise NotImplementedError("beam search decodes incrementally only (Translator(incremental=True))")
+        return B
+
+    def _max_cols(self, model_inputs):
+        """the widest score row of the batch: V + X columns, X the copied OOV words of a video (``oov_word_dict``, element 8 of the list)"""
+        x = [len(d) for d in model_inputs[8]] if self.model_config.model_mode != "video" else []
+        return self.model_config.vocab_size + max(x + [0])
+
+    def _translate_beam(self, model_inputs, B, ctl, key, n_best):
+        if ctl["block_ngram_scope"] == "paragraph":
+            ops.check_paragraph_cols(self._max_cols(model_inputs))
+        return self._translate(model_inputs, self.model, decode=Decode(BEAM, B, controls=ctl, ctl_key=key, n_best=n_best))
 
     SAMPLING = dict(random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0)
 
@@ -241,15 +348,12 @@ class Translator(object):
         if unknown:
             raise TypeError("unknown sampling keyword(s): %s" % ", ".join(sorted(unknown)))
         val = {k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.SAMPLING.items()}
-        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
-         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
-        n_oov = [len(d) for d in oov_word_dict] if self.model_config.model_mode != "video" else [0]
-        s = check_sampling(self.max_t_len, num_samples=num_samples, seed=seed, max_cols=self.model_config.vocab_size + max(n_oov + [0]), **val)
+        s = check_sampling(self.max_t_len, num_samples=num_samples, seed=seed, max_cols=self._max_cols(model_inputs), **val)
         if not self.incremental:
             raise NotImplementedError("sampling decodes incrementally only (Translator(incremental=True))")
-        key = ("sample", s["num_samples"], s["random_sampling_temp"], s["random_sampling_topk"], s["random_sampling_topp"], s["min_length"])
-        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
-                               ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=s["num_samples"], sample=(key, s["seed"]))
+        R = s["num_samples"]
+        return self._translate(model_inputs, self.model, decode=Decode(SAMPLE, R, n_best=R, seed=s["seed"], sampling=tuple(
+            s[k] for k in ("random_sampling_temp", "random_sampling_topk", "random_sampling_topp", "min_length"))))
 
     def clean_captions(self, dec_seq_list, row=0, remove_dup=True):
         """The captions the reference submits, on the device (``ops.clean_captions``): ``dec_seq_list`` as any
@@ -282,18 +386,8 @@ class Translator(object):
             o += s
         return mask_list, extra_list
 
-    def _translate_beam(self, model_inputs, B, ctl, key, n_best):
-        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
-         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
-        if ctl["block_ngram_scope"] == "paragraph" and self.model_config.model_mode != "video":     # (score rows of V + X columns)
-            ops.check_paragraph_cols(self.model_config.vocab_size + max([len(d) for d in oov_word_dict] + [0]))
-        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids,
-                               ingr_sep_masks, ingr_id_dict, oov_word_dict, batch_step_num, self.model, beam=B, ctl=(ctl, key),
-                               n_best=n_best)
-
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
-    def _prepare(self, model, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev, beam=0, ctl=None, ranked=False,
-                 sample=None):
+    def _prepare(self, model, decode, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev):
         cfg = model.config
         mode = cfg.model_mode
         Lt, V = cfg.max_t_len, cfg.vocab_size
@@ -301,49 +395,45 @@ class Translator(object):
         dicts = ingr_id_dict if mode != "video" else [{}] * N
         n_oov = [len(d) if mode != "video" else 0 for d in oov_word_dict]
         key = (tuple(int(v) for v in batch_step_num), sep_t.numpy().tobytes(), tuple(n_oov), S_pad, N, L, str(dev), self.incremental,
-               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts), beam,
-               ctl[1] if ctl is not None else None, ranked, sample)
-        prep = self._preps.get(key)
-        if prep is not None:
-            return prep
+               tuple(tuple((int(e), tuple(int(i) for i in lst)) for e, lst in d.items()) for d in dicts)) + decode.key
+        dp = self._preps.get(key)
+        if dp is not None:
+            return dp
         spans = model.ingredient_embeddings.spans(sep_t)   # one host read per batch structure
         plan = model.plan_for(batch_step_num, spans[3], S_pad, N, L, dev)
-        T = plan.T
+        T, W = plan.T, decode.width
         c_list = [V + x_ for x_ in n_oov]
-        prep = dict(key=key, spans=spans, plan=plan, c_list=c_list, T=T,
-                    pl=model._ptr_plan(dicts, c_list, Lt, plan.step_ne, plan.row_vid),
-                    row_x=Idx([n_oov[b] for b in plan.row_vid.host]),
-                    pl1=model._ptr_plan(dicts, c_list, 1, plan.step_ne, plan.step_vid),
-                    row_x1=Idx([n_oov[b] for b in plan.step_vid.host]), seq_cross={}, graph=None, beam=beam)
-        if beam:
-            # hypothesis rows t·B + h: the pointer plan of B rows per sentence (ptr_attn_gate / ptr_mix_loss with lt = B)
-            row_vid = Idx([b for b in plan.step_vid.host for _ in range(beam)])
-            prep.update(plb=model._ptr_plan(dicts, c_list, beam, plan.step_ne, row_vid), row_xb=Idx([n_oov[b] for b in row_vid.host]),
-                        seq_self_b={}, ranked=ranked)
-            if ranked:
-                # the controls' device tables live as long as the prep: a replayed graph reads the addresses it captured
-                c = ctl[0]
-                n = c["block_ngram_repeat"]
-                prep["ctl"] = dict(
-                    min_length=c["min_length"], block_ngram_repeat=n,
-                    exclusion=(exclusion_bitmap(c["exclusion_tokens"], V, dev), V) if n and c["exclusion_tokens"] else None,
-                    lp=(torch.tensor(length_penalty_table(c["length_penalty_name"], c["length_penalty_alpha"], Lt), dtype=torch.float64,
-                                     device=dev) if c["length_penalty_name"] != "none" else None))
-                if c["block_ngram_scope"] == "paragraph":
-                    prep["para"] = self._paragraph_rounds(model, plan, dicts, c_list, n_oov, beam, Lt, dev)
-            if sample is not None:
-                # sampling: every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed
-                # source (fixed, value) and the seed the decode used are captured device words
-                _, R, temp, topk, topp, m = sample
-                TR = T * R
-                prep.update(sample=dict(temp=temp, topk=topk, topp=topp, min_length=m), c_max=prep["plb"]["c_max"],
-                            key_rows=(torch.arange(TR, dtype=torch.int32, device=dev).unsqueeze(1) * Lt +
-                                      torch.arange(Lt, dtype=torch.int32, device=dev)).contiguous(),
-                            seed_src=torch.zeros(2, dtype=torch.int64, device=dev), seed_used=torch.zeros(1, dtype=torch.int64, device=dev))
+        dp = DecodePlan(key=key, spans=spans, plan=plan, c_list=c_list, T=T, kind=decode.kind, width=W, ranked=decode.ranked)
+        if not self.incremental:
+            dp.ptr_all, dp.x_all = model._ptr_plan(dicts, c_list, Lt, plan.step_ne, plan.row_vid), Idx([n_oov[b] for b in plan.row_vid.host])
+        else:
+            # hypothesis rows t·W + h: the pointer plan of W rows per sentence (ptr_attn_gate / ptr_mix_loss with lt = W)
+            row_vid = plan.step_vid if decode.kind == GREEDY else Idx([b for b in plan.step_vid.host for _ in range(W)])
+            dp.ptr_hyp, dp.x_hyp = model._ptr_plan(dicts, c_list, W, plan.step_ne, row_vid), Idx([n_oov[b] for b in row_vid.host])
+        if decode.ranked:
+            # the controls' device tables live as long as the plan: a replayed graph reads the addresses it captured
+            c = decode.controls
+            n = c["block_ngram_repeat"]
+            dp.controls = dict(
+                min_length=c["min_length"], block_ngram_repeat=n,
+                exclusion=(exclusion_bitmap(c["exclusion_tokens"], V, dev), V) if n and c["exclusion_tokens"] else None,
+                lp=(torch.tensor(length_penalty_table(c["length_penalty_name"], c["length_penalty_alpha"], Lt), dtype=torch.float64,
+                                 device=dev) if c["length_penalty_name"] != "none" else None))
+            if c["block_ngram_scope"] == "paragraph":
+                dp.rounds = self._paragraph_rounds(model, plan, dicts, c_list, n_oov, W, Lt, dev)
+                dp.rows_max = max(rd.n for rd in dp.rounds) * W
+        if decode.kind == SAMPLE:
+            # every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed source (fixed,
+            # value) and the seed the decode used are captured device words
+            temp, topk, topp, m = decode.sampling
+            dp.sampling = dict(temp=temp, topk=topk, topp=topp, min_length=m, max_cols=dp.ptr_hyp["c_max"])
+            dp.key_rows = (torch.arange(T * W, dtype=torch.int32, device=dev).unsqueeze(1) * Lt +
+                           torch.arange(Lt, dtype=torch.int32, device=dev)).contiguous()
+            dp.seed_src, dp.seed_used = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
         if len(self._preps) > 32:
             self._preps.clear()
-        self._preps[key] = prep
-        return prep
+        self._preps[key] = dp
+        return dp
 
     @staticmethod
     def _paragraph_rounds(model, plan, dicts, c_list, n_oov, B, Lt, dev):
@@ -362,21 +452,21 @@ class Translator(object):
             Ns = len(sent)
             TB = Ns * B
             row_vid = Idx([b for b in vids for _ in range(B)])
-            rd = dict(n=Ns, step_ne=Idx([ne[t] for t in sent]), row_vid=row_vid, row_xb=Idx([n_oov[b] for b in row_vid.host]),
-                      desc=Idx([v for b in vids for v in (off[b], s_)]), sent32=Idx(sent),
-                      mem_rows=Idx([t * n_mem + j for t in sent for j in range(n_mem)]),
-                      seq_cross=SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, None),
-                      seq_self=[SeqInfo.uniform(TB, 1, i + 1, None) for i in range(Lt - 1)])
-            rd["plb"] = model._ptr_plan(dicts, c_list, B, rd["step_ne"], row_vid)
-            up.add(np.asarray(sent, dtype=np.int64).view(np.int32), sink=lambda t, rd=rd: rd.__setitem__("sent64", t.view(torch.int64)))
-            for v in (rd["step_ne"], row_vid, rd["row_xb"], rd["desc"], rd["sent32"], rd["mem_rows"]) + tuple(
-                    rd["plb"][k] for k in ("csr_off", "csr_ent", "csr_id", "csr_w", "row_c")):
+            rd = SimpleNamespace(n=Ns, step_ne=Idx([ne[t] for t in sent]), row_vid=row_vid, row_xb=Idx([n_oov[b] for b in row_vid.host]),
+                                 desc=Idx([v for b in vids for v in (off[b], s_)]), sent32=Idx(sent),
+                                 mem_rows=Idx([t * n_mem + j for t in sent for j in range(n_mem)]),
+                                 seq_cross=SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, None),
+                                 seq_self=[SeqInfo.uniform(TB, 1, i + 1, None) for i in range(Lt - 1)])
+            rd.plb = model._ptr_plan(dicts, c_list, B, rd.step_ne, row_vid)
+            up.add(np.asarray(sent, dtype=np.int64).view(np.int32), sink=lambda t, rd=rd: setattr(rd, "sent64", t.view(torch.int64)))
+            for v in (rd.step_ne, row_vid, rd.row_xb, rd.desc, rd.sent32, rd.mem_rows) + tuple(
+                    rd.plb[k] for k in ("csr_off", "csr_ent", "csr_id", "csr_w", "row_c")):
                 up.add_idx(v)
-            for sq in [rd["seq_cross"]] + rd["seq_self"]:
+            for sq in [rd.seq_cross] + rd.seq_self:
                 up.add_seq(sq)
             rounds.append(rd)
         up.flush()
-        return dict(rounds=rounds, rows_max=max(rd["n"] for rd in rounds) * B)
+        return rounds
 
     def _text_table(self, model, Lt, cx, dev):
         """(Lt, V, D): text_embeddings(token v at position p) for every (p, v) — inference weights are constant, so the embedding stack
@@ -396,10 +486,12 @@ class Translator(object):
         return self._ttab[1]
 
     # ------------------------------------------------------------------ device part: encoder side once, then the decoding iterations
-    def _decode_core(self, model, prep, feats, ids_all, masks_all, ingr_ids_flat):
+    def _decode_core(self, model, dp, feats, ids_all, masks_all, ingr_ids_flat):
+        """→ (ids (T, K, Lt) int32, cum (T, K) fp32 or None, len (T, K) int32 or None): K = 1 (greedy, the plain beam: the chosen
+        caption), B (ranked: final-key order) or R (samples in sample order)"""
         cfg = model.config
         mode = cfg.model_mode
-        plan, T = prep["plan"], prep["T"]
+        plan, T = dp.plan, dp.T
         dev = feats.device
         Lt, D = cfg.max_t_len, cfg.hidden_size
         cx = _Ctx(cfg, False, model.rng(dev))
@@ -411,7 +503,7 @@ class Translator(object):
                 e.record()
                 stamps.append(e)
         stamp()
-        ents = model.ingredient_embeddings.run(ingr_ids_flat, prep["spans"], cx)
+        ents = model.ingredient_embeddings.run(ingr_ids_flat, dp.spans, cx)
         cls = model._encode_clips(feats, plan.video_rows, ops.take_rows(ids_all, plan.video_rows),
                                   ops.take_rows(masks_all, plan.video_rows), plan.seq_enc, cx,
                                   cls_only=(plan.cls_rows_dev, plan.seq_enc_cls))
@@ -432,131 +524,76 @@ class Translator(object):
             bank = None
 
         stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
-        if prep.get("para") is not None:
-            out = self._paragraph_iterations(model, prep, mem, bank, cx, tab=self._text_table(model, Lt, cx, dev))
-            stamp()
-            return out
-        if prep["beam"]:
-            out = self._beam_iterations(model, prep, mem, bank, cx, tab=self._text_table(model, Lt, cx, dev))
-            stamp()
-            return out
+        if not self.incremental:
+            out = self._greedy_rerun(model, dp, mem, bank, cx)
+        else:
+            side = _DecoderSide(model, cx, mem, bank, self._text_table(model, Lt, cx, dev), T)
+            loop = (self._sample_iterations if dp.kind == SAMPLE else self._paragraph_iterations if dp.rounds is not None else
+                    self._beam_iterations if dp.kind == BEAM else self._greedy_iterations)
+            out = loop(dp, side)
+        stamp()
+        return out
+
+    @staticmethod
+    def _greedy_iterations(dp, side):
+        """greedy, incremental: the Lt iterations over the T sentences, each a row of its own (no ancestry table, group 1)"""
+        cfg = side.model.config
+        T, Lt, dev = dp.T, cfg.max_t_len, side.wide[0].device
         text = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
         ext = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
         nxt = torch.full((T,), BOS, dtype=torch.int32, device=dev)
         nxt_ext = nxt.clone()
-        if self.incremental:
-            n_mem = mem.shape[0] // T
-            layers = model.decoder.layer
-            caches = [torch.zeros(T * Lt, 2 * D, dtype=torch.float32, device=dev) for _ in layers]
-            st = model.decoder.stacked_memory_kv()
-            if st is not None:                 # one projection of the memory rows for the whole stack; each layer reads its columns
-                mem_kv = ops.split_cols(ops.linear(mem, st[0], st[1]), len(layers))
-            else:
-                mem_kv = [layer.memory_kv(mem) for layer in layers]
-            proj = model.bank_projection(bank) if bank is not None else None
-            seq_cross = prep["seq_cross"].get(n_mem)
-            if seq_cross is None:
-                seq_cross = prep["seq_cross"][n_mem] = ops.SeqInfo(list(range(T)), [1] * T, [s_ * n_mem for s_ in range(T)],
-                                                                   [n_mem] * T, dev)
-            pl1, row_x1 = prep["pl1"], prep["row_x1"]
-            tab = self._text_table(model, Lt, cx, dev)
-            text[:, 0] = nxt                    # (position i + 1 of both id matrices is written by iteration i's pick)
-            ext[:, 0] = nxt_ext
-            for i in range(Lt):
-                seq_self = plan.seq_dec_incremental(i, Lt, dev)
-                # the text embedding of (token, position) from the per-checkpoint table: one row gather instead of
-                # LayerNorm(300) → projection → LayerNorm + position encoding per iteration
-                x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
-                for layer, cache, kv in zip(layers, caches, mem_kv):
-                    x = layer.step(x, i, Lt, cache, kv, seq_self, seq_cross, cx)
-                if mode == "video":
-                    scores = model.decoder_classifier.run(x, cx.eps)          # raw logits (translator.py:159)
-                else:
-                    scores, _ = model._lm_probs(x, bank, pl1, cx, proj=proj)
-                nxt_ext, nxt = ops.greedy_pick(scores, pl1["row_c"], row_x1, 1, 0, UNK, append=(text, ext, i + 1) if i + 1 < Lt else None)
-        else:
-            pl, row_x = prep["pl"], prep["row_x"]
-            tmask = torch.zeros(T, Lt, dtype=torch.float32, device=dev)
-            for i in range(Lt):
-                text[:, i] = nxt
-                ext[:, i] = nxt_ext
-                tmask[:, i] = 1.0
-                xt = model.text_embeddings.run(text.reshape(-1), Lt, cx)
-                dec = model.decoder.run(xt, tmask.reshape(-1), mem, plan.seq_dec_self, plan.seq_dec_cross, None, cx)
-                if mode == "video":
-                    scores = model.decoder_classifier.run(dec, cx.eps)          # raw logits (translator.py:159)
-                else:
-                    scores, _ = model._lm_probs(dec, bank, pl, cx)
-                nxt_ext, nxt = ops.greedy_pick(scores, pl["row_c"], row_x, Lt, i, UNK)
-        stamp()
-        return text if mode == "video" else ext
-
-    def _beam_iterations(self, model, prep, mem, bank, cx, tab):
-        """The Lt − 1 selection steps of a beam decode over the T·B hypothesis rows → (ids (T, Lt) int32, score (T,) fp32); with controls
-        or n-best (``prep["ranked"]``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order.  Sampling
-        (``prep["sample"]``): the same iterations over the T·R sample rows, every row its own ancestry, ``ops.sample_step`` in place of the
-        selection → (ids (T·R, Lt) int32, cum (T·R,) fp32, len (T·R,) int32)."""
-        cfg = model.config
-        mode = cfg.model_mode
-        B, T = prep["beam"], prep["T"]
-        TB = T * B
-        dev = mem.device
-        Lt, D = cfg.max_t_len, cfg.hidden_size
-        n_mem = mem.shape[0] // T
-        layers = model.decoder.layer
-        caches = [torch.zeros(TB * Lt, 2 * D, dtype=torch.float32, device=dev) for _ in layers]     # one slot of Lt rows per hypothesis
-        st = model.decoder.stacked_memory_kv()
-        if st is not None:
-            mem_kv = ops.split_cols(ops.linear(mem, st[0], st[1]), len(layers))
-        else:
-            mem_kv = [layer.memory_kv(mem) for layer in layers]
-        proj = model.bank_projection(bank) if bank is not None else None
-        key = ("beam", n_mem)
-        seq_cross = prep["seq_cross"].get(key)
-        if seq_cross is None:          # (the fallback's segmentation: hypothesis r over the memory rows of its sentence r // B)
-            seq_cross = prep["seq_cross"][key] = SeqInfo(list(range(TB)), [1] * TB, [(r // B) * n_mem for r in range(TB)], [n_mem] * TB, dev)
-        plb, row_xb = prep["plb"], prep["row_xb"]
-        samp = prep.get("sample")
-        if samp is None:
-            toks, cum = self._beam_start(T, B, Lt, dev)
-        else:
-            # sampling: one (text ids, extended ids) pair written in place; every sample starts alive at BOS
-            text = torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev)
-            text[:, 0] = BOS
-            ext = text.clone()
-            cum = torch.zeros(TB, dtype=torch.float32, device=dev)
-            ops.sample_seed(prep["seed_src"], self._seed_word_on(dev), prep["seed_used"])
-        fin = torch.zeros(TB, dtype=torch.int32, device=dev)
-        nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
-        ranked = prep["ranked"]                   # decoding controls and / or n-best: lengths tracked, the finals sorted by their key
-        ctl = prep.get("ctl")
-        length = torch.zeros(TB, dtype=torch.int32, device=dev) if ranked or samp is not None else None
-        for i in range(Lt - 1):
-            t_in, t_out = (toks[i % 2], toks[(i + 1) % 2]) if samp is None else (None, None)
-            rows = t_in[2] if samp is None else prep["key_rows"]
-            seq_self = prep["seq_self_b"].get(i)
-            if seq_self is None:
-                seq_self = prep["seq_self_b"][i] = SeqInfo.uniform(TB, 1, i + 1, dev)
-            scores = self._hyp_scores(model, cx, tab, nxt, i, caches, mem_kv, seq_self, seq_cross, rows, B, bank, plb, proj)
-            if samp is not None:
-                _, nxt = ops.sample_step(scores, plb["row_c"], row_xb, i, mode == "video", UNK, EOS, PAD, cum, fin, length, text, ext,
-                                         prep["seed_used"], temp=samp["temp"], topk=samp["topk"], topp=samp["topp"],
-                                         min_length=samp["min_length"], max_cols=prep["c_max"])
-            elif ranked:
-                _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
-                                          length=length, **ctl)
-            else:
-                _, _, nxt = ops.beam_step(scores, plb["row_c"], row_xb, B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt)
-        if samp is not None:
-            return ext, cum, length
-        if ranked:           # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
-            return ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
-        return ops.beam_finalize(cum, toks[(Lt - 1) % 2][1], B)
+        caches, rows, seq_cross = side.caches(T), side.rows(), side.seq_cross(dp)
+        text[:, 0] = nxt                    # (position i + 1 of both id matrices is written by iteration i's pick)
+        ext[:, 0] = nxt_ext
+        for i in range(Lt):
+            scores = side.scores(rows, dp.ptr_hyp, nxt, i, caches, dp.plan.seq_dec_incremental(i, Lt, dev), seq_cross)
+            nxt_ext, nxt = ops.greedy_pick(scores, dp.ptr_hyp["row_c"], dp.x_hyp, 1, 0, UNK, append=(text, ext, i + 1) if i + 1 < Lt else None)
+        return (text if cfg.model_mode == "video" else ext).unsqueeze(1), None, None
 
     @staticmethod
-    def _beam_start(n_sent, B, Lt, dev):
-        """the first step's tables of a beam decode over n_sent·B hypothesis rows: the ping-pong (text ids, extended ids, KV-cache ancestry)
-        pairs — children are written from their parents' rows — with BOS and the row's own slot at position 0, and cum (beam 0 alone)"""
+    def _greedy_rerun(model, dp, mem, bank, cx):
+        """greedy, ``incremental=False``: every iteration re-runs all Lt positions, as the reference does (the parity tests' reference form)"""
+        cfg = model.config
+        mode, plan, T, Lt, dev = cfg.model_mode, dp.plan, dp.T, cfg.max_t_len, mem.device
+        text = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
+        ext = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
+        nxt = torch.full((T,), BOS, dtype=torch.int32, device=dev)
+        nxt_ext = nxt.clone()
+        tmask = torch.zeros(T, Lt, dtype=torch.float32, device=dev)
+        for i in range(Lt):
+            text[:, i] = nxt
+            ext[:, i] = nxt_ext
+            tmask[:, i] = 1.0
+            xt = model.text_embeddings.run(text.reshape(-1), Lt, cx)
+            dec = model.decoder.run(xt, tmask.reshape(-1), mem, plan.seq_dec_self, plan.seq_dec_cross, None, cx)
+            if mode == "video":
+                scores = model.decoder_classifier.run(dec, cx.eps)          # raw logits (translator.py:159)
+            else:
+                scores, _ = model._lm_probs(dec, bank, dp.ptr_all, cx)
+            nxt_ext, nxt = ops.greedy_pick(scores, dp.ptr_all["row_c"], dp.x_all, Lt, i, UNK)
+        return (text if mode == "video" else ext).unsqueeze(1), None, None
+
+    @staticmethod
+    def _self_segs(dp, Lt, dev):
+        """the self-attention segmentations of the T·width hypothesis rows: at iteration i every row over its i + 1 ancestry rows"""
+        if dp.seq_self is None:
+            dp.seq_self = [SeqInfo.uniform(dp.T * dp.width, 1, i + 1, dev) for i in range(Lt - 1)]
+        return dp.seq_self
+
+    def _beam_iterations(self, dp, side):
+        """A beam decode over the T·B hypothesis rows of the whole batch → (ids (T, 1, Lt) int32, score (T, 1) fp32, None); with controls
+        or n-best (``dp.ranked``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order."""
+        return self._beam_search(dp, side, side.rows(), dp.T, dp.ptr_hyp, dp.x_hyp, side.caches(dp.T * dp.width),
+                                 self._self_segs(dp, side.model.config.max_t_len, side.wide[0].device), side.seq_cross(dp))
+
+    @staticmethod
+    def _beam_search(dp, side, rows, n_sent, ptr, row_x, caches, seq_self, seq_cross, history=None):
+        """The Lt − 1 selection steps of a beam decode over n_sent·B hypothesis rows, then the final pick.  The ping-pong (text ids,
+        extended ids, KV-cache ancestry) pairs — children are written from their parents' rows — start with BOS and the row's own slot at
+        position 0, cum with beam 0 alone.  ``history``: ``ops.beam_step``'s, of a paragraph round."""
+        cfg = side.model.config
+        B, Lt, dev = dp.width, cfg.max_t_len, side.wide[0].device
         TB = n_sent * B
         toks = [[torch.full((TB, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
         toks[0][0][:, 0] = BOS
@@ -564,66 +601,63 @@ class Translator(object):
         toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
         cum = torch.zeros(n_sent, B, dtype=torch.float32, device=dev)
         cum[:, 1:] = float("-inf")                                             # the first step: beam 0 alone
-        return toks, cum.view(TB)
+        cum = cum.view(TB)
+        fin = torch.zeros(TB, dtype=torch.int32, device=dev)
+        nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
+        length = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.ranked else None       # ranked: lengths tracked
+        ctl = dict(dp.controls, length=length, history=history) if dp.ranked else {}
+        for i in range(Lt - 1):
+            t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
+            scores = side.scores(rows, ptr, nxt, i, caches, seq_self[i], seq_cross, t_in[2], B)
+            _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt, **ctl)
+        ext = toks[(Lt - 1) % 2][1]
+        if dp.ranked:        # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
+            return ops.beam_finalize_nbest(cum, ext, B, B, length, dp.controls["lp"])
+        ids, score = ops.beam_finalize(cum, ext, B)
+        return ids.unsqueeze(1), score.unsqueeze(1), None
 
-    @staticmethod
-    def _hyp_scores(model, cx, tab, nxt, i, caches, mem_kv, seq_self, seq_cross, rows, B, bank, plb, proj):
-        """one decoding iteration over hypothesis rows → their score rows: the text embedding of tokens ``nxt`` at position i, the layers
-        over each row's ancestry ``rows`` in the KV caches (B rows per sentence share its memory K|V), then the head — raw logits in
-        ``video`` mode (the step score is their log_softmax) — or the pointer-generator's probabilities"""
-        x = ops.take_rows(tab[i], nxt) if tab is not None else model.text_embeddings.run_at(nxt, i, cx)
-        for layer, cache, kv in zip(model.decoder.layer, caches, mem_kv):
-            x = layer.step(x, i, model.config.max_t_len, cache, kv, seq_self, seq_cross, cx, key_rows=rows, q_group=B)
-        if model.config.model_mode == "video":
-            return model.decoder_classifier.run(x, cx.eps)
-        return model._lm_probs(x, bank, plb, cx, proj=proj)[0]
-
-    def _paragraph_iterations(self, model, prep, mem, bank, cx, tab):
+    def _paragraph_iterations(self, dp, side):
         """A paragraph-scope beam decode: the Lt − 1 selection steps (svpc_beam_step_para) run once per round, round s over the N_s·B
         rows of sentence s of every video with S_b > s, reading the chosen captions of rounds 0 … s − 1 from the decode's (T, Lt) top-1
         matrix.  Each round gathers its sentences' rows of the memory K|V projection, the pointer bank and its projection; the per-layer
         KV caches are sized for the largest round and reused (a round reads only rows it wrote).  → (ids (T, B, Lt) int32, cum (T, B)
         fp32, len (T, B) int32) in final-key order, as ``_beam_iterations`` with controls."""
-        cfg = model.config
-        mode = cfg.model_mode
-        B, T = prep["beam"], prep["T"]
-        dev = mem.device
-        Lt, D = cfg.max_t_len, cfg.hidden_size
-        layers = model.decoder.layer
-        para, ctl = prep["para"], prep["ctl"]
-        caches = [torch.zeros(para["rows_max"] * Lt, 2 * D, dtype=torch.float32, device=dev) for _ in layers]
-        st = model.decoder.stacked_memory_kv()
-        wide = [ops.linear(mem, st[0], st[1])] if st is not None else [layer.memory_kv(mem) for layer in layers]
-        proj = model.bank_projection(bank) if bank is not None else None
+        B, T, Lt, dev = dp.width, dp.T, side.model.config.max_t_len, side.wide[0].device
+        caches = side.caches(dp.rows_max)
         ids = torch.full((T, B, Lt), PAD, dtype=torch.int32, device=dev)
         cums = torch.empty(T, B, dtype=torch.float32, device=dev)
         lens = torch.empty(T, B, dtype=torch.int32, device=dev)
         top1 = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)        # the chosen captions: the later rounds' history
-        for rd in para["rounds"]:
-            Ns = rd["n"]
-            TB = Ns * B
-            mem_rows, sent = rd["mem_rows"].dev(dev), rd["sent32"].dev(dev)
-            kv = [ops.take_rows_f32(w, mem_rows) for w in wide]
-            mem_kv = ops.split_cols(kv[0], len(layers)) if st is not None else kv
-            bank_r = ops.take_rows_f32(bank.reshape(T, -1), sent).view(Ns, *bank.shape[1:]) if bank is not None else None
-            proj_r = ops.take_rows_f32(proj.reshape(T, -1), sent).view(Ns, *proj.shape[1:]) if proj is not None else None
-            toks, cum = self._beam_start(Ns, B, Lt, dev)
-            fin = torch.zeros(TB, dtype=torch.int32, device=dev)
-            length = torch.zeros(TB, dtype=torch.int32, device=dev)
-            nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
-            cache_r = [c[:TB * Lt] for c in caches]
-            for i in range(Lt - 1):
-                t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
-                scores = self._hyp_scores(model, cx, tab, nxt, i, cache_r, mem_kv, rd["seq_self"][i], rd["seq_cross"], t_in[2], B, bank_r,
-                                          rd["plb"], proj_r)
-                _, _, nxt = ops.beam_step(scores, rd["plb"]["row_c"], rd["row_xb"], B, i, mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out,
-                                          Lt, length=length, history=(top1, rd["desc"], BOS), **ctl)
-            r_ids, r_cum, r_len = ops.beam_finalize_nbest(cum, toks[(Lt - 1) % 2][1], B, B, length, ctl["lp"])
-            ids.index_copy_(0, rd["sent64"], r_ids)
-            cums.index_copy_(0, rd["sent64"], r_cum)
-            lens.index_copy_(0, rd["sent64"], r_len)
-            top1.index_copy_(0, rd["sent64"], r_ids[:, 0])
+        for rd in dp.rounds:
+            r_ids, r_cum, r_len = self._beam_search(dp, side, side.rows(rd), rd.n, rd.plb, rd.row_xb, [c[:rd.n * B * Lt] for c in caches],
+                                                    rd.seq_self, rd.seq_cross, history=(top1, rd.desc, BOS))
+            ids.index_copy_(0, rd.sent64, r_ids)
+            cums.index_copy_(0, rd.sent64, r_cum)
+            lens.index_copy_(0, rd.sent64, r_len)
+            top1.index_copy_(0, rd.sent64, r_ids[:, 0])
         return ids, cums, lens
+
+    def _sample_iterations(self, dp, side):
+        """A sampling decode: the Lt − 1 steps over the T·R sample rows, every row alive at BOS and its own ancestry (``dp.key_rows``),
+        one (text ids, extended ids) pair written in place by ``ops.sample_step`` → (ids (T, R, Lt) int32, cum (T, R) fp32, len (T, R)
+        int32) in sample order."""
+        cfg = side.model.config
+        R, T, Lt, dev = dp.width, dp.T, cfg.max_t_len, side.wide[0].device
+        n = T * R
+        text = torch.full((n, Lt), PAD, dtype=torch.int32, device=dev)
+        text[:, 0] = BOS
+        ext = text.clone()
+        cum = torch.zeros(n, dtype=torch.float32, device=dev)
+        ops.sample_seed(dp.seed_src, self._seed_word_on(dev), dp.seed_used)
+        fin = torch.zeros(n, dtype=torch.int32, device=dev)
+        nxt = torch.full((n,), BOS, dtype=torch.int32, device=dev)
+        length = torch.zeros(n, dtype=torch.int32, device=dev)
+        caches, rows, seq_self, seq_cross = side.caches(n), side.rows(), self._self_segs(dp, Lt, dev), side.seq_cross(dp)
+        for i in range(Lt - 1):
+            scores = side.scores(rows, dp.ptr_hyp, nxt, i, caches, seq_self[i], seq_cross, dp.key_rows, R)
+            _, nxt = ops.sample_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, length,
+                                     text, ext, dp.seed_used, **dp.sampling)
+        return ext.view(T, R, Lt), cum.view(T, R), length.view(T, R)
 
     def _seed_word_on(self, dev):
         """the sampling decodes' seed word (int64 (1,) on ``dev``): drawn once from torch's default generator, then advanced on the device
@@ -636,18 +670,15 @@ class Translator(object):
     def translate_batch_greedy(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list,
                                ingr_input_ids, ingr_masks, ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions,
                                batch_step_num, rt_model):
-        return self._translate(input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
-                               ingr_id_dict, oov_word_dict, batch_step_num, rt_model)
+        return self._translate([input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
+                                ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num], rt_model, decode=Decode())
 
-    def _translate(self, input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_sep_masks,
-                   ingr_id_dict, oov_word_dict, batch_step_num, rt_model, beam=0, ctl=None, n_best=0, sample=None):
-        model = rt_model
+    def _translate(self, model_inputs, model, decode):
+        (input_ids_list, video_features_list, input_masks_list, token_type_ids_list, ingr_input_ids, ingr_masks,
+         ingr_sep_masks, ingr_id_dict, oov_word_dict, alignments, actions, batch_step_num) = model_inputs
         dev = video_features_list[0].device
-        ranked = bool(beam) and (n_best > 0 or (ctl is not None and ctl[1] is not None))
-        if sample is not None:
-            sample, seed = sample
-            if dev.type != "cuda":
-                raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
+        if decode.kind == SAMPLE and dev.type != "cuda":
+            raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
         # tensors are consecutive slices of one buffer (the usual collate output; model._stacked sees it) that is three launches on the
         # stacked views instead of three per step
@@ -670,26 +701,26 @@ class Translator(object):
 
         def part(lo, hi, stream=None):
             n = hi - lo
-            prep = self._prepare(model, list(batch_step_num[lo:hi]), sep_all[lo:hi], list(ingr_id_dict[lo:hi]), list(oov_word_dict[lo:hi]),
-                                 S_pad, n, L, dev, beam=beam, ctl=ctl, ranked=ranked, sample=sample)
-            if sample is not None:       # the seed source of this call: a captured input, like the batch tensors
-                prep["seed_src"].copy_(torch.tensor([0, 0] if seed is None else [1, seed], dtype=torch.int64))
+            dp = self._prepare(model, decode, list(batch_step_num[lo:hi]), sep_all[lo:hi], list(ingr_id_dict[lo:hi]),
+                               list(oov_word_dict[lo:hi]), S_pad, n, L, dev)
+            if dp.seed_src is not None:       # the seed source of this call: a captured input, like the batch tensors
+                dp.seed_src.copy_(torch.tensor([0, 0] if decode.seed is None else [1, decode.seed], dtype=torch.int64))
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
-                out = self._decode_core(model, prep, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
+                out = self._decode_core(model, dp, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
                                         src[2].reshape(-1).float(), src[3].reshape(-1))
             else:
-                out = self._decode_graphed(model, prep, src, (S_pad, n, L, F), stream)
-            if sample is not None:
-                self.last_sample_seed = prep["seed_used"].clone()
-            return prep["plan"], out
+                out = self._decode_graphed(model, dp, src, (S_pad, n, L, F), stream)
+            if dp.seed_used is not None:
+                self.last_sample_seed = dp.seed_used.clone()
+            return dp.plan, out
 
         # Two halves on two streams: the encoder side of a batch is bound by the matrix cores, the Lt decoding
         # iterations are chains of small dependent launches that leave the chip idle — two independent chains interleave.  Videos are
         # independent (the reference decodes them one by one, translator.py:175-191), so the ids are those of the unsplit decode bit for
         # bit (tests/test_config5_gpu.py).  Two replayed graphs on two streams, not one forked graph.
         halves = [(0, N)]
-        if self.graph and self.two_streams and not beam and dev.type == "cuda" and N >= 2 * self.min_half:
+        if self.graph and self.two_streams and decode.kind == GREEDY and dev.type == "cuda" and N >= 2 * self.min_half:
             halves = [(0, N // 2), (N // 2, N)]
         if len(halves) == 1:
             plans_outs = [part(0, N)]
@@ -705,32 +736,24 @@ class Translator(object):
                     plans_outs.append(part(lo, hi, st))
             for st in (sa, sb):
                 cur.wait_stream(st)
+        # every strategy's result: ids (T, K, Lt), cum (T, K) or None, len (T, K) or None.  The call returns the first n_best of the K rows
+        # per sentence, or (n_best 0) the chosen caption alone, without lengths
+        k = decode.n_best
         res, scores, lens = [], [], []
-        for plan, out in plans_outs:
-            score = length = None
-            if sample is not None:
-                out, score, length = out
-                R = beam
-                out, score, length = out.view(-1, R, out.shape[1]), score.view(-1, R), length.view(-1, R).to(torch.int64)
-            elif ranked:
-                out, score, length = out
-                k = n_best or 1                        # (translate_batch_beam: row 0; translate_batch_nbest: the first n_best rows)
-                out, score, length = (out[:, :k], score[:, :k], length[:, :k].to(torch.int64)) if n_best else (out[:, 0], score[:, 0].contiguous(), None)
-            elif beam:
-                out, score = out
-            out = out.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
+        for plan, (ids, cum, length) in plans_outs:
+            if k:
+                ids, cum, length = ids[:, :k], cum[:, :k], length[:, :k].to(torch.int64)
+            else:
+                ids, cum, length = ids[:, 0], cum[:, 0].contiguous() if cum is not None else None, None
+            ids = ids.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
                 o, n_ = plan.h_step_off[b], plan.h_step_len[b]
-                res.append(out[o:o + n_])
-                if beam:
-                    scores.append(score[o:o + n_])
-                if length is not None:
-                    lens.append(length[o:o + n_])
-        if beam:
-            return res, oov_word_dict, scores, lens
-        return res, oov_word_dict
+                for lst, t in ((res, ids), (scores, cum), (lens, length)):
+                    if t is not None:
+                        lst.append(t[o:o + n_])
+        return (res, oov_word_dict, scores, lens) if scores else (res, oov_word_dict)
 
-    def _decode_graphed(self, model, prep, src, shape, stream=None):
+    def _decode_graphed(self, model, dp, src, shape, stream=None):
         """The ≈2,000 launches of a batch's decode (encoder side + Lt iterations × 6 layers) replayed as ONE hipGraph.  The graph
         is tied to the batch structure (step / ingredient / OOV counts: ``_prepare``'s key): the first batch of a structure runs
         eagerly twice (warm-up: index tables reach the device, kernels set their attributes) and is then captured; later batches of
@@ -750,13 +773,11 @@ class Translator(object):
         sig = (tuple(p.data_ptr() for p in list(model.parameters())[:8]), _ops.get_precision(),
                id(getattr(model, "_svpc_weight_store", None)), WEIGHTS_EPOCH[0],
                tuple(p._version for p in [te.word_embeddings.weight] + list(te.word_fc.parameters())), side.cuda_stream)
-        if not isinstance(prep["graph"], dict):
-            prep["graph"] = {}                       # one graph per replay stream: two halves of ONE structure must not share captured buffers
-        gkey = side.cuda_stream
-        g = prep["graph"].get(gkey)
+        gkey = side.cuda_stream                      # one graph per replay stream: two halves of ONE structure must not share captured buffers
+        g = dp.graphs.get(gkey)
         if g is not None and g[3] != sig:
             g = None
-            prep["graph"].pop(gkey, None)
+            dp.graphs.pop(gkey, None)
 
         def flat(st):
             return (st[0].view(S_pad * n * L, F), st[1].view(-1), st[2].view(-1), st[3].view(-1))
@@ -771,17 +792,17 @@ class Translator(object):
             # structure would pin another 256 MB kernel workspace each (ops._ws is per (device, stream))
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                self._decode_core(model, prep, *flat(static))
-                self._decode_core(model, prep, *flat(static))
+                self._decode_core(model, dp, *flat(static))
+                self._decode_core(model, dp, *flat(static))
             cur.wait_stream(side)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             from .graph import capturing
             with capturing(graph, stream=side):
-                out = self._decode_core(model, prep, *flat(static))
-            g = prep["graph"][gkey] = (graph, static, out, sig)
+                out = self._decode_core(model, dp, *flat(static))
+            g = dp.graphs[gkey] = (graph, static, out, sig)
         graph, static, out, _ = g
         for dst, s_ in zip(static, src):
             dst.copy_(s_)
         graph.replay()
-        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
+        return tuple(o.clone() if o is not None else None for o in out)

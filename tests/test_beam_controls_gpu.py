@@ -257,7 +257,7 @@ def test_graph_replay_equals_eager_with_controls(golden_dir, case, mt):
             for a, b in zip(e[k], g[k]):
                 assert torch.equal(a, b)
     graphed.translate_batch_beam(syn.translate_inputs(batch), 4)          # another setting: its own prep and graph
-    assert len(graphed._preps) == 2 and all(p["graph"] for p in graphed._preps.values())
+    assert len(graphed._preps) == 2 and all(p.graphs for p in graphed._preps.values())
 
 
 @pytest.mark.parametrize("graph", [False, True])

@@ -235,7 +235,7 @@ def test_graph_replay_equals_eager(golden_dir, case, mt):
         d1, _, s1 = graphed.translate_batch_beam(syn.translate_inputs(batch), 4)
         for a, b, sa, sb in zip(d0, d1, s0, s1):
             assert torch.equal(a, b) and torch.equal(sa, sb)
-    assert len(graphed._preps) == 1 and next(iter(graphed._preps.values()))["graph"]
+    assert len(graphed._preps) == 1 and next(iter(graphed._preps.values())).graphs
 
 
 # ------------------------------------------------------------------------------------------------ 6. config 5 at its headline size

@@ -494,7 +494,7 @@ def test_graphed_decode_equals_eager_decode(golden_dir, case, mt):
         if rep == 0:
             for b, d in enumerate(got):
                 np.testing.assert_array_equal(d.cpu().numpy(), z["decode/%d" % b])
-    assert len(tr_g._preps) == 1 and next(iter(tr_g._preps.values()))["graph"] is not None
+    assert len(tr_g._preps) == 1 and next(iter(tr_g._preps.values())).graphs
 
 
 @pytest.mark.parametrize("mt,steps,n_ingr,n_oov", [

@@ -265,7 +265,7 @@ def test_graph_replay_equals_eager_for_two_batches(golden_dir):
             for x, y in zip(e[k], g[k]):
                 assert torch.equal(x, y)
         outs.append(g[0])
-    assert len(graphed._preps) == 1 and all(p["graph"] for p in graphed._preps.values())
+    assert len(graphed._preps) == 1 and all(p.graphs for p in graphed._preps.values())
     assert any(not torch.equal(x, y) for x, y in zip(outs[0], outs[1]))
     _assert_no_repeated_gram(outs[0], 1, (7,))
 

@@ -281,7 +281,7 @@ def test_seeds_eager_and_replayed(golden_dir, case, mt):
                 assert torch.equal(a, b)
         assert int(graphed.last_sample_seed) == 99
         graphed.translate_batch_sample(syn.translate_inputs(batch), 4, **kw)
-    assert len(graphed._preps) == 1 and next(iter(graphed._preps.values()))["graph"]
+    assert len(graphed._preps) == 1 and next(iter(graphed._preps.values())).graphs
     # seed=None: consecutive replays of the one captured graph draw different samples, from different seeds
     a = graphed.translate_batch_sample(syn.translate_inputs(batch), 4, **kw)
     sa = int(graphed.last_sample_seed)

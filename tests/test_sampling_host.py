@@ -120,8 +120,8 @@ def test_opt_attributes_are_read_and_seed_is_not(tiny, monkeypatch):
     monkeypatch.setattr(tr, "_translate", fake)
     with pytest.raises(StopIteration):
         tr.translate_batch_sample(syn.translate_inputs(tiny[1]), 2, random_sampling_topk=3)
-    key, seed = seen["sample"]
-    assert key == ("sample", 2, 0.25, 3, 0.0, 0) and seed is None and seen["beam"] == 2
+    d = seen["decode"]
+    assert (d.kind, d.width, d.sampling, d.n_best) == ("sample", 2, (0.25, 3, 0.0, 0), 2) and d.seed is None
 
 
 # ------------------------------------------------------------------------------------------------ the selection rule
