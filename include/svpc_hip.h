@@ -578,6 +578,33 @@ int svpc_caption_ingredients(const int* words, const int* len, int n_rows, int l
                              const int* ing_tok, const int* tok_row, const unsigned* tok_oov, const int* eq_ids, const unsigned* oov_a,
                              const unsigned* gt_mask, const int* gt_len, const int* gx_off, const int* gx_ids, long long* masks, int* extra,
                              int* row_counts, int* vid_counts, unsigned long long* acc, svpc_stream_t stream);
+/* ---- Bleu_1..4, ROUGE_L and CIDEr of clean captions against reference paragraphs (densevid_eval/para-evaluate.py:26-29, 71-84, 112-125 with
+ *      Bleu(4) option `closest`, Rouge beta = 1.2, Cider() n = 4 sigma = 6; the definitions: DESIGN 11.6), on the device.  A token is an id
+ *      1 … 65534 of the host's token lexicon (svpc_amd/caption_scores.py).  An n-gram (n <= 4) is the 64-bit key t0 | t1 << 16 | t2 << 32 |
+ *      t3 << 48 of its ids, absent fields 0.  The gram -> idf table (tab_key, tab_idf; tab_cap a power of two; key 0 = empty slot; built on
+ *      the host, only probed here) is open addressing with linear probing from slot (h ^ (h >> 32)) & (tab_cap - 1), h = key *
+ *      0x9E3779B97F4A7C15 (mod 2^64); a gram absent from it has idf log_docs = ln(number of reference videos).
+ *      vid (n_vid, 12) int32 = {n_ref <= 4, index of the video in the reference set, X <= 128 copied words, oov0, ref_off[4], ref_len[4]}.
+ * svpc_caption_tokens: the token stream of video b's clean captions (rows vid_off[b] … vid_off[b + 1] - 1 of words / len as
+ * svpc_caption_clean writes them, in order): word id w < vocab gives voc_tok[voc_off[w] … voc_off[w + 1] - 1], copied id vocab + x (x < X)
+ * gives oov_tok[oov_off[oov0 + x] … oov_off[oov0 + x + 1] - 1], any other id nothing.  Out: tokens (n_vid, 1024) int32 (zero-filled past
+ * the end) and tok_len (n_vid,) — -1 for a video over 1024 tokens (the host refuses what could get there). */
+int svpc_caption_tokens(const int* words, const int* len, const int* vid_off, int n_vid, int lt, int vocab, const int* voc_off,
+                        const int* voc_tok, int n_voc_tok, const int* vid, const int* oov_off, int n_oov_off, const int* oov_tok,
+                        int n_oov_tok, int* tokens, int* tok_len, svpc_stream_t stream);
+/* per video: reference r = the ref_len[r] <= 1024 16-bit tokens at ref_tok + ref_off[r] (n_ref_tok in all), ref_norm (n_vid, 4, 4) its
+ * CIDEr norms per n (fp64, from the host), gauss[d] = exp(-d^2 / 72) for d = 0 … 1023.  counts (n_vid, 11) int32 = correct_1..4 (clipped
+ * n-gram matches), guess_1..4 (max(0, testlen - n + 1)), testlen, reflen (closest reference length, ties to the shorter), the largest LCS;
+ * scores (n_vid, 6) fp64 = the video's own Bleu_1..4, ROUGE_L, CIDEr; every fp64 sum in a fixed order (the same inputs give the same
+ * bits).  seen (or NULL): seen[index of the video] = 1 (n_seen entries).  A video whose tok_len is -1: counts -1, scores 0. */
+int svpc_caption_score_counts(const int* tokens, const int* tok_len, int n_vid, const int* vid, const double* ref_norm,
+                              const unsigned short* ref_tok, long long n_ref_tok, const unsigned long long* tab_key, const double* tab_idf,
+                              int tab_cap, double log_docs, const double* gauss, int* counts, double* scores, long long* seen, int n_seen,
+                              svpc_stream_t stream);
+/* acc_i[0..10] += sums of correct_1..4, guess_1..4, testlen, reflen and the number of videos (64-bit integers), acc_f[0..1] += sum of
+ * ROUGE_L, sum of CIDEr over the n_vid rows (a thread's rows in index order, then a fixed tree: deterministic); rows of -1 are left out. */
+int svpc_caption_score_accum(const int* counts, const double* scores, int n_vid, unsigned long long* acc_i, double* acc_f,
+                             svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

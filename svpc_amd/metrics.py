@@ -9,7 +9,8 @@ updated by two small kernels per video; ``result()`` is the only host read-back.
 (src/translate.py:27-42 and :81-83, recursive_caption_dataset.py:472-500, densevid_eval/evaluateRepetition.py,
 evaluateCaptionsDiversity.py:219-282, get_caption_stat.py) from the translator's id matrices, three launches per batch and no host
 synchronisation until ``result()``.  ``IngredientF1`` adds the ingredient-prediction recall / precision / F1 of
-src/calculate_ingredient_f1.py from the same clean captions.
+src/calculate_ingredient_f1.py from the same clean captions, ``CaptionScores`` Bleu_1…4, ROUGE_L and CIDEr against
+reference paragraphs (densevid_eval/para-evaluate.py without METEOR).
 """
 from __future__ import annotations
 
@@ -204,4 +205,77 @@ class IngredientF1:
         c, p, r = (int(x) for x in self.acc.cpu())
         res = compute_total_f1(c, r, p)
         res.update(n_correct=c, n_recall=r, n_precision=p)
+        return res
+
+
+class CaptionScores:
+    """Running Bleu_1…4, ROUGE_L and CIDEr of an evaluation epoch against a ``caption_scores.ReferenceCorpus``, kept on the device — the
+    numbers densevid_eval/para-evaluate.py gives src/train.py:278-331 apart from METEOR (the scores are pinned to the
+    published definitions restated there, not to outputs of the third-party scorer).
+
+    ``update(dec_seq_list, plan, row=0, clean=None)`` takes what any ``translate_batch*`` returns and ``corpus.plan(videos)`` of the same
+    videos; ``clean=(words, len)`` reuses a clean-up already made with run collapse on (``DecodeMetrics.last_clean`` after its ``update``
+    of the same result and row), otherwise one ``ops.clean_captions`` call is made.  Then three launches — token streams, per-video
+    counts and scores, accumulation — with nothing uploaded for a recurring batch, so ``update`` can be captured once its structure has
+    been seen; integer totals by integer adds and the two fp64 sums in a fixed order, so a given sequence of updates always gives the same
+    bits.  ``result()`` is the only read-back.  Updating one video twice in an epoch counts it twice: that is the caller's error.
+
+    ``state`` (int64): [correct_1..4, guess_1..4, testlen, reflen, videos | Σ ROUGE_L, Σ CIDEr (float64 bits) | one flag per video of the
+    reference set].  ``last_counts`` (N, 11) int32 and ``last_scores`` (N, 6) float64: the last update's per-video correct_1..4,
+    guess_1..4, testlen, reflen, largest LCS and Bleu_1..4, ROUGE_L, CIDEr."""
+
+    KEYS = ("Bleu_1", "Bleu_2", "Bleu_3", "Bleu_4", "ROUGE_L", "CIDEr")
+
+    def __init__(self, corpus):
+        self.corpus = corpus
+        self.device = torch.device(corpus.device)
+        if self.device.type != "cuda":
+            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.state = torch.zeros(13 + corpus.n_docs, dtype=torch.int64, device=self.device)
+        self.acc_i, self.acc_f, self.seen = self.state[:11], self.state[11:13].view(torch.float64), self.state[13:]
+        self.last_counts = self.last_scores = None
+
+    def reset(self):
+        self.state.zero_()
+        self.last_counts = self.last_scores = None
+
+    def update(self, dec_seq_list, plan, row=0, clean=None):
+        if plan.corpus is not self.corpus:
+            raise ValueError("the plan was made by another reference corpus")
+        ids, steps = ops.stack_captions(dec_seq_list)
+        lt = ids.shape[-1]
+        ops.check_caption_metrics(lt, ids.dtype, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
+        if not ids.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
+        if clean is None:
+            clean = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        words, ln = clean
+        if tuple(words.shape) != (ids.shape[0], lt):
+            raise ValueError("clean=(words, len) must be the clean-up of these %d rows of %d positions" % (ids.shape[0], lt))
+        tokens, tok_len = ops.caption_tokens(words, ln, plan, steps)
+        counts, scores = ops.caption_score_counts(tokens, tok_len, plan, seen=self.seen)
+        ops.caption_score_accum(counts, scores, self.acc_i, self.acc_f)
+        self.last_counts, self.last_scores = counts, scores
+        return scores
+
+    def result(self, missing="skip"):
+        """The single host read-back → Bleu_1 … Bleu_4 (from the totals), ROUGE_L and CIDEr (means over the videos), num_videos, testlen,
+        reflen, correct, guess.  ``missing="empty"``: every video of the reference set not updated yet counts as an empty hypothesis, as
+        ``evaluate_para`` treats a missing prediction (testlen += 0, reflen += its shortest reference, scores 0, means over all videos)."""
+        from .caption_scores import bleu_from_totals
+        if missing not in ("skip", "empty"):
+            raise ValueError("missing must be 'skip' or 'empty', got %r" % (missing,))
+        host = self.state.cpu()
+        v = [int(x) for x in host[:11]]
+        rouge, cider = (float(x) for x in host[11:13].view(torch.float64))
+        nv, reflen = v[10], v[9]
+        if missing == "empty":
+            for i, s in enumerate(host[13:].tolist()):
+                if not s:
+                    nv += 1
+                    reflen += self.corpus.min_ref_len[i]
+        bleu = bleu_from_totals(v[0:4], v[4:8], v[8], reflen) if nv else [0.0] * 4
+        res = {k: b for k, b in zip(self.KEYS, bleu)}
+        res.update(ROUGE_L=rouge / nv if nv else 0.0, CIDEr=cider / nv if nv else 0.0, num_videos=nv, testlen=v[8], reflen=reflen,
+                   correct=v[0:4], guess=v[4:8])
         return res

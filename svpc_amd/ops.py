@@ -2982,3 +2982,77 @@ def caption_ingredients(words, length, plan, acc=None, steps=None):
               plan.ptr("tok_oov"), plan.ptr("eq_ids"), plan.ptr("oov_a"), plan.ptr("gt_mask"), plan.ptr("gt_len"), plan.ptr("gx_off"),
               plan.ptr("gx_ids"), _p(masks), _p(extra), _p(row_counts), _p(vid_counts), _p(acc), _stream())
     return masks, extra, row_counts, vid_counts
+
+
+CAPTION_TOKENS = 1024           # tokens of one video's hypothesis paragraph (and of a reference): they live in the workgroup's LDS
+CAPTION_SCORE_COUNT_COLS = 11   # correct_1..4, guess_1..4, testlen, reflen, lcs
+CAPTION_SCORE_COLS = 6          # Bleu_1..4, ROUGE_L, CIDEr
+
+
+def caption_tokens(words, length, plan, steps):
+    """The token stream of every video's clean captions (svpc_caption_tokens): ``words`` (T, Lt) / ``length`` (T,) int32 as
+    ``clean_captions`` returns them (run collapse on), ``plan`` a ``caption_scores.ScorePlan``, ``steps`` the videos' row counts →
+    (tokens (N, 1024) int32 lexicon ids, zero past the end; tok_len (N,) int32).  ValueError when a video's hypothesis could exceed 1,024
+    tokens (S_b · (Lt − 1) · the longest expansion of a word)."""
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("caption_tokens: words must be contiguous int32 (T, Lt)")
+    T, lt = words.shape
+    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
+        raise ValueError("caption_tokens: len must be contiguous int32 (T,)")
+    steps = [int(s) for s in steps]
+    check_caption_metrics(lt)
+    if len(steps) != plan.n_vid or sum(steps) != T or any(s < 0 for s in steps):
+        raise ValueError("caption_tokens: the plan's %d video(s) with rows %r do not add up to T = %d" % (plan.n_vid, steps, T))
+    plan.check_cap(steps, lt)
+    if plan.buf.device != words.device:
+        raise ValueError("caption_tokens: the plan lives on %s, the captions on %s" % (plan.buf.device, words.device))
+    _need_gpu(words)
+    cp, N = plan.corpus, plan.n_vid
+    vid_off = plan.vid_off(steps)
+    tokens = torch.empty(N, CAPTION_TOKENS, dtype=torch.int32, device=words.device)
+    tok_len = torch.empty(N, dtype=torch.int32, device=words.device)
+    _lib.call("caption_tokens", _p(words), _p(length), _p(vid_off), N, lt, cp.V, _p(cp.voc_off), _p(cp.voc_tok), cp.voc_tok.numel(),
+              plan.ptr("vid"), plan.ptr("oov_off"), plan.size("oov_off"), plan.ptr("oov_tok"), plan.size("oov_tok"), _p(tokens), _p(tok_len),
+              _stream())
+    return tokens, tok_len
+
+
+def caption_score_counts(tokens, tok_len, plan, seen=None):
+    """Per-video Bleu / ROUGE_L / CIDEr counts and scores (svpc_caption_score_counts): ``tokens`` (N, 1024) / ``tok_len``
+    (N,) int32 as ``caption_tokens`` returns them, ``plan`` the same ``ScorePlan``; ``seen``: a contiguous int64 device tensor with one
+    entry per video of the reference set (the entries of this batch's videos are set to 1) →
+    (counts (N, 11) int32: correct_1..4, guess_1..4, testlen, reflen, the largest LCS; scores (N, 6) float64: the video's own Bleu_1..4,
+    ROUGE_L, CIDEr)."""
+    N = plan.n_vid
+    if tokens.dtype != torch.int32 or tuple(tokens.shape) != (N, CAPTION_TOKENS) or not tokens.is_contiguous():
+        raise ValueError("caption_score_counts: tokens must be contiguous int32 (%d, %d)" % (N, CAPTION_TOKENS))
+    if tok_len.dtype != torch.int32 or tuple(tok_len.shape) != (N,) or not tok_len.is_contiguous():
+        raise ValueError("caption_score_counts: tok_len must be contiguous int32 (%d,)" % N)
+    if plan.buf.device != tokens.device:
+        raise ValueError("caption_score_counts: the plan lives on %s, the tokens on %s" % (plan.buf.device, tokens.device))
+    cp = plan.corpus
+    if seen is not None and (seen.dtype != torch.int64 or seen.numel() != cp.n_docs or not seen.is_contiguous() or seen.device != tokens.device):
+        raise ValueError("caption_score_counts: seen must be a contiguous int64 (%d,) tensor on the tokens' device" % cp.n_docs)
+    _need_gpu(tokens)
+    counts = torch.empty(N, CAPTION_SCORE_COUNT_COLS, dtype=torch.int32, device=tokens.device)
+    scores = torch.empty(N, CAPTION_SCORE_COLS, dtype=torch.float64, device=tokens.device)
+    _lib.call("caption_score_counts", _p(tokens), _p(tok_len), N, plan.ptr("vid"), plan.ptr("ref_norm"), _p(cp.ref_tok), cp.n_ref_tok,
+              _p(cp.tab_key), _p(cp.tab_idf), cp.table_capacity, cp.log_docs, _p(cp.gauss), _p(counts), _p(scores), _p(seen),
+              0 if seen is None else cp.n_docs, _stream())
+    return counts, scores
+
+
+def caption_score_accum(counts, scores, acc_i, acc_f):
+    """acc_i (11,) int64 += Σ (correct_1..4, guess_1..4, testlen, reflen, 1), acc_f (2,) float64 += Σ (ROUGE_L, CIDEr) over the rows —
+    svpc_caption_score_accum (integer adds; the fp64 sums in a fixed order)."""
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != CAPTION_SCORE_COUNT_COLS or not counts.is_contiguous():
+        raise ValueError("caption_score_accum: counts must be contiguous int32 (N, %d)" % CAPTION_SCORE_COUNT_COLS)
+    if scores.dtype != torch.float64 or tuple(scores.shape) != (counts.shape[0], CAPTION_SCORE_COLS) or not scores.is_contiguous():
+        raise ValueError("caption_score_accum: scores must be contiguous float64 (N, %d)" % CAPTION_SCORE_COLS)
+    if acc_i.dtype != torch.int64 or acc_i.numel() != 11 or not acc_i.is_contiguous() or acc_i.device != counts.device:
+        raise ValueError("caption_score_accum: acc_i must be a contiguous int64 (11,) tensor on the counts' device")
+    if acc_f.dtype != torch.float64 or acc_f.numel() != 2 or not acc_f.is_contiguous() or acc_f.device != counts.device:
+        raise ValueError("caption_score_accum: acc_f must be a contiguous float64 (2,) tensor on the counts' device")
+    _need_gpu(counts)
+    _lib.call("caption_score_accum", _p(counts), _p(scores), counts.shape[0], _p(acc_i), _p(acc_f), _stream())
+    return acc_i, acc_f

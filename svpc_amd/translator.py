@@ -105,7 +105,9 @@ of those, up to the first EOS, runs of one word collapsed — ``convert_ids_to_s
 ``ids_to_sentences(clean, lens, idx2word, oov_word_dict)`` builds the strings on the host.  ``svpc_amd.metrics.DecodeMetrics`` counts
 the reference's repetition / diversity numbers from the same ids.  ``Translator.caption_ingredients(dec_seq_list, plan,
 row=0)`` tells which of a recipe's ingredients each caption mentions (the rule of src/calculate_ingredient_f1.py, on the device;
-``svpc_amd.metrics.IngredientF1`` accumulates its recall / precision / F1 — DESIGN §11.5).  ``translate_batch*`` themselves do not change.
+``svpc_amd.metrics.IngredientF1`` accumulates its recall / precision / F1 — DESIGN §11.5).  ``Translator.caption_scores(dec_seq_list,
+plan, row=0)`` gives every video's Bleu_1…4, ROUGE_L and CIDEr against its reference paragraphs on the device
+(``svpc_amd.metrics.CaptionScores`` accumulates the epoch's — DESIGN §11.6).  ``translate_batch*`` themselves do not change.
 """
 from __future__ import annotations
 
@@ -385,6 +387,15 @@ class Translator(object):
             extra_list.append(extra[o:o + s])
             o += s
         return mask_list, extra_list
+
+    def caption_scores(self, dec_seq_list, plan, row=0):
+        """Bleu_1…4, ROUGE_L and CIDEr of every video's decoded paragraph against its references (``ops.caption_score_counts``; DESIGN
+        §11.6): ``dec_seq_list`` as any ``translate_batch*`` returns it, ``plan`` = ``ReferenceCorpus.plan(videos)`` of the same videos →
+        (N, 6) float64 on the device, e.g. to rank n-best rows or samples.  No host synchronisation."""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        tokens, tok_len = ops.caption_tokens(words, ln, plan, steps)
+        return ops.caption_score_counts(tokens, tok_len, plan)[1]
 
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
     def _prepare(self, model, decode, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev):
