@@ -26,12 +26,12 @@ import re
 import numpy as np
 import torch
 
+from .caption_plan import CAP_COPIED, PackedTables, PlanCompiler, RowTables, copied_words, vocabulary
 from .ingredients import ascii_word
 
 CAP_TOKENS = 1024           # tokens of a hypothesis and of a reference: both sit in the workgroup's LDS
 CAP_REFS = 4
 CAP_LEXICON = 65534         # token ids 1 … 65534: four 16-bit fields make an exact 64-bit gram key
-CAP_COPIED = 128            # copied (OOV) words of one video, ids V … V + 127
 VID_COLS = 12               # n_ref, corpus index, X, oov0, ref_off[4], ref_len[4]
 SIGMA = 6.0
 HASH_MUL = 0x9E3779B97F4A7C15
@@ -65,13 +65,12 @@ def _gram_counts(tok, n):
     return c
 
 
-class ScorePlan:
+class ScorePlan(PackedTables):
     """A batch's device tables: [ref_norm (N, 4, 4) float64 | vid (N, 12) | oov_off | oov_tok] int32 in one buffer; ``vid_off(steps)``
     adds the (N + 1,) table of the videos' first rows for a decode's (S_b) structure, cached."""
 
     def __init__(self, corpus, compiled, device):
         self.corpus = corpus
-        self.device = device
         self.n_vid = len(compiled)
         self.index = [c["index"] for c in compiled]
         self.max_expansion = [max(corpus.voc_expansion, c["expansion"]) for c in compiled]
@@ -89,39 +88,12 @@ class ScorePlan:
                 oov_off.append(len(oov_tok))
                 oov_tok += t
             oov_off.append(len(oov_tok))
-        parts = dict(ref_norm=norms.reshape(-1).view(np.int32), vid=np.array(vid, dtype=np.int32),
-                     oov_off=np.array(oov_off, dtype=np.int32), oov_tok=np.array(oov_tok + [0], dtype=np.int32))
-        self.sections, flat, o = {}, [], 0
-        for name, a in parts.items():
-            self.sections[name] = (o, a.size)
-            flat.append(a)
-            o += a.size
-        self.buf = torch.from_numpy(np.concatenate(flat)).to(device)          # the batch's one upload (the float64 section comes first)
-        self._offs = {}
-
-    def section(self, name):
-        o, n = self.sections[name]
-        return self.buf[o:o + n]
-
-    def ptr(self, name):
-        return self.buf.data_ptr() + 4 * self.sections[name][0]
-
-    def size(self, name):
-        return self.sections[name][1]
+        super().__init__(dict(ref_norm=norms, vid=np.array(vid, dtype=np.int32), oov_off=np.array(oov_off, dtype=np.int32),
+                              oov_tok=np.array(oov_tok + [0], dtype=np.int32)), device)        # (the float64 section comes first)
+        self._offs = RowTables()
 
     def vid_off(self, steps):
-        key = tuple(int(s) for s in steps)
-        if len(key) != self.n_vid or any(s < 0 for s in key):
-            raise ValueError("the plan holds %d video(s), got the row counts %r" % (self.n_vid, list(key)))
-        t = self._offs.get(key)
-        if t is None:
-            off = [0]
-            for s in key:
-                off.append(off[-1] + s)
-            if len(self._offs) > 32:
-                self._offs.clear()
-            t = self._offs[key] = torch.tensor(off, dtype=torch.int32, device=self.device)
-        return t
+        return self._offs.table(steps, self.device, self.n_vid)
 
     def check_cap(self, steps, lt):
         """ValueError when a video's hypothesis could exceed 1,024 tokens: S_b · (Lt − 1) · (longest expansion of a word)"""
@@ -131,20 +103,19 @@ class ScorePlan:
                                  % (b, s, int(lt) - 1, self.max_expansion[b], CAP_TOKENS))
 
 
-class ReferenceCorpus:
+class ReferenceCorpus(PlanCompiler):
     """Built once per evaluation set: ``idx2word`` (a list, or a dict id → word covering 0 … V − 1), ``references`` (video key → 1 … 4
     reference paragraph strings — a single string counts as one — as ``import_ground_truths`` holds them; the documents of CIDEr's idf are
     the videos of this whole set), the device the tables live on.  ``table_capacity``: slots of the gram table (a power of two above the
-    number of grams; default: at most half full)."""
+    number of grams; default: at most half full).
+
+    ``plan(videos)``: one dict per video with ``key`` (a key of ``references``) and ``oov_word_dict`` (word → extended id) → the batch's
+    ScorePlan.  ``compile_video(video)``: one video's host tables; ValueError for a key outside the reference set, copied ids outside
+    V … V + 127 or used twice."""
 
     def __init__(self, idx2word, references, device="cuda", table_capacity=None):
-        self.device = torch.device(device)
-        if isinstance(idx2word, dict):
-            if sorted(idx2word) != list(range(len(idx2word))):
-                raise ValueError("idx2word must cover the ids 0 … V − 1")
-            idx2word = [idx2word[i] for i in range(len(idx2word))]
-        if not len(idx2word):
-            raise ValueError("an empty vocabulary")
+        super().__init__(device)
+        idx2word = vocabulary(idx2word)
         if not len(references):
             raise ValueError("no references")
         self.V = len(idx2word)
@@ -225,8 +196,6 @@ class ReferenceCorpus:
         self.tab_key = torch.from_numpy(self.table_keys.view(np.int64).copy()).to(self.device)
         self.tab_idf = torch.from_numpy(self.table_idf.copy()).to(self.device)
         self.gauss = torch.from_numpy(self.gauss_host.copy()).to(self.device)
-        self._videos = {}
-        self._plans = {}
 
     def _token_id(self, w):
         i = self._tok.get(w)
@@ -264,43 +233,15 @@ class ReferenceCorpus:
     def video_key(video):
         return (video["key"], tuple(sorted((video.get("oov_word_dict") or {}).items())))
 
-    def compile_video(self, video):
-        """One video's host tables (cached): ValueError for a key outside the reference set, copied ids outside V … V + 127 or used twice."""
-        key = self.video_key(video)
-        c = self._videos.get(key)
-        if c is not None:
-            return c
+    def _compile(self, video):
         if video["key"] not in self.index_of:
             raise ValueError("video %r is not in the reference set" % (video["key"],))
-        oov = {}
-        for w, i in (video.get("oov_word_dict") or {}).items():
-            if isinstance(i, bool) or int(i) != i or not self.V <= int(i) < self.V + CAP_COPIED:
-                raise ValueError("copied word %r: its id %r is outside V … V + %d (at most %d copied words per video)"
-                                 % (w, i, CAP_COPIED - 1, CAP_COPIED))
-            if int(i) in oov:
-                raise ValueError("copied id %d is used twice" % int(i))
-            oov[int(i)] = [self._token_id(t) for t in parse_sent(ascii_word(w))]
-        X = max(oov) - self.V + 1 if oov else 0
-        tokens = [oov.get(self.V + x, []) for x in range(X)]          # (an id no word of the video spells gives no token)
-        c = dict(index=self.index_of[video["key"]], tokens=tokens, expansion=max([1] + [len(t) for t in tokens]))
-        if len(self._videos) > 4096:
-            self._videos.clear()
-        self._videos[key] = c
-        return c
+        tokens = copied_words(video.get("oov_word_dict"), self.V, lambda w: [self._token_id(t) for t in parse_sent(ascii_word(w))],
+                              missing=[])                                 # (an id no word of the video spells gives no token)
+        return dict(index=self.index_of[video["key"]], tokens=tokens, expansion=max([1] + [len(t) for t in tokens]))
 
-    def plan(self, videos):
-        """``videos``: one dict per video with ``key`` (a key of ``references``) and ``oov_word_dict`` (word → extended id) → the batch's
-        ScorePlan.  Plans are cached per tuple of video keys (bounded): a recurring batch uploads nothing."""
-        if not len(videos):
-            raise ValueError("no videos to plan")
-        key = tuple(self.video_key(v) for v in videos)
-        p = self._plans.get(key)
-        if p is None:
-            compiled = [self.compile_video(v) for v in videos]
-            if len(self._plans) > 32:
-                self._plans.clear()
-            p = self._plans[key] = ScorePlan(self, compiled, self.device)
-        return p
+    def _plan(self, compiled):
+        return ScorePlan(self, compiled, self.device)
 
 
 def bleu_from_totals(correct, guess, testlen, reflen):

@@ -22,9 +22,10 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .caption_plan import CAP_COPIED, PackedTables, PlanCompiler, RowTables, copied_words, vocabulary
+
 CAP_INGREDIENTS = 64        # E_b: one bit of the 64-bit mask per listed ingredient
 CAP_TOKENS = 128            # pattern tokens of one video
-CAP_COPIED = 128            # copied (OOV) words of one video: four 32-bit words per predicate
 CONTAINS, ENDS, EQUALS, STARTS = 0, 1, 2, 3
 VID_COLS = 8                # ing0, E, X, eq0, n_eq, gt0, n_gt, (unused)
 
@@ -80,13 +81,12 @@ def masks_to_names(masks, ingredients):
     return [[ing for e, ing in enumerate(ingredients) if (int(m) >> e) & 1] for m in vals]
 
 
-class IngredientPlan:
+class IngredientPlan(PackedTables):
     """A batch's device tables (see the module docstring); ``rows(steps)`` adds the row → (video, step) table of a decode's (S_b)
     structure, cached, so a recurring structure uploads nothing."""
 
     def __init__(self, lexicon, compiled, device):
         self.lexicon = lexicon
-        self.device = device
         self.n_vid = len(compiled)
         self.ingredients = [c["ingredients"] for c in compiled]
         self.gt_steps = [len(c["gt"]) if c["gt"] is not None else None for c in compiled]
@@ -110,22 +110,8 @@ class IngredientPlan:
                      tok_oov=np.concatenate(tok_oov) if tok_oov else np.zeros(0, np.uint32), eq_ids=np.array(eq_ids, dtype=np.int64),
                      oov_a=np.concatenate(oov_a) if oov_a else np.zeros(0, np.uint32), gt_mask=np.array(gt_mask, dtype=np.uint32),
                      gt_len=np.array(gt_len, dtype=np.int64), gx_off=np.array(gx_off, dtype=np.int64), gx_ids=np.array(gx_ids, dtype=np.int64))
-        self.sections, flat, o = {}, [], 0
-        for name, a in parts.items():
-            a32 = a.view(np.int32) if a.dtype == np.uint32 else a.astype(np.int32)
-            self.sections[name] = (o, a32.size)
-            flat.append(a32)
-            o += a32.size
-        self.buf = torch.from_numpy(np.concatenate(flat)).to(device)          # the batch's one upload
-        self._rows = {}
-
-    def section(self, name):
-        """a section of the packed buffer as an int32 view (tests; the kernel takes ``ptr(name)``)"""
-        o, n = self.sections[name]
-        return self.buf[o:o + n]
-
-    def ptr(self, name):
-        return self.buf.data_ptr() + 4 * self.sections[name][0]
+        super().__init__(parts, device)
+        self._rows = RowTables(rows=True)
 
     def default_steps(self):
         if not self.has_gt:
@@ -134,36 +120,22 @@ class IngredientPlan:
 
     def rows(self, steps):
         """[vid_off (N + 1) | (video, step) of every row (2 T)] int32 on the device for the videos' row counts ``steps``"""
-        key = tuple(int(s) for s in steps)
-        if len(key) != self.n_vid or any(s < 0 for s in key):
-            raise ValueError("the plan holds %d video(s), got the row counts %r" % (self.n_vid, list(key)))
-        t = self._rows.get(key)
-        if t is None:
-            off, vs = [0], []
-            for b, s in enumerate(key):
-                off.append(off[-1] + s)
-                for i in range(s):
-                    vs += [b, i]
-            if len(self._rows) > 32:
-                self._rows.clear()
-            t = self._rows[key] = torch.tensor(off + vs, dtype=torch.int32, device=self.device)
-        return t
+        return self._rows.table(steps, self.device, self.n_vid)
 
 
-class IngredientLexicon:
+class IngredientLexicon(PlanCompiler):
     """Built once per vocabulary: ``idx2word`` (a list, or a dict id → word covering 0 … V − 1), ``all_ingredients`` (the global set A),
     the device the tables live on.  ``table`` is the (capacity, ⌈V / 32⌉) int32 predicate bitmap (``n_rows`` rows in use), ``a_bits`` the
-    (⌈V / 32⌉,) map of the vocabulary words in A."""
+    (⌈V / 32⌉,) map of the vocabulary words in A.
+
+    ``plan(videos)``: one dict per video with ``ingredients`` (raw strings, duplicates kept), ``oov_word_dict`` (word → extended id) and
+    optionally ``gt_sentences`` (and ``key``, any hashable that names the video; default: its content) → the batch's IngredientPlan.
+    ``compile_video(video)``: one video's host tables; ValueError for an empty ingredient, a copied word that is empty or holds a blank,
+    copied ids outside V … V + 127 or used twice, more than 64 ingredients or 128 pattern tokens."""
 
     def __init__(self, idx2word, all_ingredients, device="cuda"):
-        self.device = torch.device(device)
-        if isinstance(idx2word, dict):
-            if sorted(idx2word) != list(range(len(idx2word))):
-                raise ValueError("idx2word must cover the ids 0 … V − 1")
-            idx2word = [idx2word[i] for i in range(len(idx2word))]
-        if not len(idx2word):
-            raise ValueError("an empty vocabulary")
-        self.words = [_caption_word(w, "vocabulary word") for w in idx2word]
+        super().__init__(device)
+        self.words = [_caption_word(w, "vocabulary word") for w in vocabulary(idx2word)]
         self.V = len(self.words)
         self.W = (self.V + 31) // 32
         self.A = frozenset(all_ingredients)
@@ -177,8 +149,6 @@ class IngredientLexicon:
         self.table = torch.zeros(256, self.W, dtype=torch.int32, device=self.device)
         self._uploaded = 0
         self._retired = []                  # outgrown tables stay allocated: a captured update may still read its (unchanged) rows
-        self._videos = {}
-        self._plans = {}
 
     @property
     def n_rows(self):
@@ -215,26 +185,11 @@ class IngredientLexicon:
         gt = video.get("gt_sentences")
         return (tuple(video["ingredients"]), tuple(sorted((video.get("oov_word_dict") or {}).items())), None if gt is None else tuple(gt))
 
-    def compile_video(self, video):
-        """One video's host tables (cached per video key): ValueError for an empty ingredient, a copied word that is empty or holds a
-        blank, copied ids outside V … V + 127 or used twice, more than 64 ingredients or 128 pattern tokens."""
-        key = self.video_key(video)
-        c = self._videos.get(key)
-        if c is not None:
-            return c
+    def _compile(self, video):
         ingredients = list(video["ingredients"])
         if len(ingredients) > CAP_INGREDIENTS:
             raise ValueError("a video holds at most %d ingredients (one mask bit each), got %d" % (CAP_INGREDIENTS, len(ingredients)))
-        oov = {}
-        for w, i in (video.get("oov_word_dict") or {}).items():
-            if isinstance(i, bool) or int(i) != i or not self.V <= int(i) < self.V + CAP_COPIED:
-                raise ValueError("copied word %r: its id %r is outside V … V + %d (at most %d copied words per video)"
-                                 % (w, i, CAP_COPIED - 1, CAP_COPIED))
-            if int(i) in oov:
-                raise ValueError("copied id %d is used twice" % int(i))
-            oov[int(i)] = _caption_word(w, "copied word")
-        X = max(oov) - self.V + 1 if oov else 0
-        copied = [oov.get(self.V + x) for x in range(X)]          # (None: an id no word of the video spells)
+        copied = copied_words(video.get("oov_word_dict"), self.V, lambda w: _caption_word(w, "copied word"))  # (None: an id no word spells)
         pats = [pattern(ing) for ing in ingredients]
         if sum(len(p) for p in pats) > CAP_TOKENS:
             raise ValueError("a video holds at most %d pattern tokens, got %d" % (CAP_TOKENS, sum(len(p) for p in pats)))
@@ -257,26 +212,10 @@ class IngredientLexicon:
                 mask = sum(1 << e for e, p in enumerate(pats) if _mentioned(p, words))
                 extra = [w for w in words if w not in whole and w in self.A]
                 gt.append((mask, sorted({i for w in extra for i in ids_of(w)}), bin(mask).count("1") + len(extra)))
-        c = dict(ingredients=ingredients, X=X, copied=copied, ing_off=ing_off, tok_row=tok_row,
-                 tok_oov=np.stack(tok_oov) if tok_oov else np.zeros((0, CAP_COPIED // 32), np.uint32), eq_ids=eq_ids,
-                 oov_a=_bits([w is not None and w in self.A for w in copied], CAP_COPIED // 32), gt=gt)
-        if len(self._videos) > 4096:
-            self._videos.clear()
-        self._videos[key] = c
-        return c
+        return dict(ingredients=ingredients, X=len(copied), copied=copied, ing_off=ing_off, tok_row=tok_row,
+                    tok_oov=np.stack(tok_oov) if tok_oov else np.zeros((0, CAP_COPIED // 32), np.uint32), eq_ids=eq_ids,
+                    oov_a=_bits([w is not None and w in self.A for w in copied], CAP_COPIED // 32), gt=gt)
 
-    def plan(self, videos):
-        """``videos``: one dict per video with ``ingredients`` (raw strings, duplicates kept), ``oov_word_dict`` (word → extended id) and
-        optionally ``gt_sentences`` (and ``key``, any hashable that names the video; default: its content) → the batch's IngredientPlan.
-        Plans are cached per tuple of video keys (bounded): a recurring batch uploads nothing."""
-        if not len(videos):
-            raise ValueError("no videos to plan")
-        key = tuple(self.video_key(v) for v in videos)
-        p = self._plans.get(key)
-        if p is None:
-            compiled = [self.compile_video(v) for v in videos]
-            self._sync()
-            if len(self._plans) > 32:
-                self._plans.clear()
-            p = self._plans[key] = IngredientPlan(self, compiled, self.device)
-        return p
+    def _plan(self, compiled):
+        self._sync()
+        return IngredientPlan(self, compiled, self.device)

@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib, ops
+from .caption_plan import RowTables
 from .synthetic import EOS, PAD
 
 IGNORE = -1
@@ -82,6 +83,29 @@ class TrainMetrics:
                     counts=v[:8])
 
 
+def _gpu_device(device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+    return device
+
+
+def _clean_rows(dec_seq_list, row, clean=None, video_cap=True, pad=PAD, eos=EOS, remove_dup=True):
+    """The opening of every ``update``: a decode's per-video ids as one tensor, checked (``video_cap``: with the 4096 positions a video's
+    captions may hold), on the GPU, and cleaned unless ``clean=(words, len)`` brings the clean-up → (words, len, steps, device)."""
+    ids, steps = ops.stack_captions(dec_seq_list)
+    lt = ids.shape[-1]
+    ops.check_caption_metrics(lt, ids.dtype, steps=steps if video_cap else None, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
+    if not ids.is_cuda:
+        raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
+    if clean is None:
+        clean = ops.clean_captions(ids, pad, eos, IGNORE, remove_dup, row=row)
+    words, ln = clean
+    if tuple(words.shape) != (ids.shape[0], lt):
+        raise ValueError("clean=(words, len) must be the clean-up of these %d rows of %d positions" % (ids.shape[0], lt))
+    return words, ln, steps, ids.device
+
+
 class DecodeMetrics:
     """Running repetition / diversity / caption statistics of an evaluation epoch, kept on the device.
 
@@ -98,9 +122,7 @@ class DecodeMetrics:
     FIELDS = ("re1", "re2", "re3", "re4", "div1", "div2", "div3", "div4")
 
     def __init__(self, vocab_size, device="cuda", pad=PAD, eos=EOS, period_id=None, comma_id=None, remove_dup=True):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.device = _gpu_device(device)
         self.V = int(vocab_size)
         if self.V < 1:
             raise ValueError("vocab_size must be >= 1, got %r" % (vocab_size,))
@@ -110,7 +132,7 @@ class DecodeMetrics:
         self.vocab_bits = torch.zeros((self.V + 31) // 32, dtype=torch.int32, device=self.device)
         self.last_counts = None
         self.last_clean = None              # the last update's (words, len): IngredientF1.update(..., clean=) reuses it
-        self._offs = {}
+        self._offs = RowTables()
 
     def reset(self):
         self.acc.zero_()
@@ -119,25 +141,11 @@ class DecodeMetrics:
 
     def _vid_off(self, steps, dev):
         """the (N + 1,) int32 table of the videos' first rows: uploaded once per (S_b) structure"""
-        key = (tuple(steps), str(dev))
-        t = self._offs.get(key)
-        if t is None:
-            off = [0]
-            for s in steps:
-                off.append(off[-1] + s)
-            if len(self._offs) > 32:
-                self._offs.clear()
-            t = self._offs[key] = torch.tensor(off, dtype=torch.int32, device=dev)
-        return t
+        return self._offs.table(steps, dev)
 
     def update(self, dec_seq_list, row=0):
-        ids, steps = ops.stack_captions(dec_seq_list)
-        lt = ids.shape[-1]
-        ops.check_caption_metrics(lt, ids.dtype, steps=steps, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
-        if not ids.is_cuda:
-            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
-        words, ln = ops.clean_captions(ids, self.pad, self.eos, IGNORE, self.remove_dup, row=row)
-        counts = ops.caption_ngram_counts(words, ln, self._vid_off(steps, ids.device), self.V, self.period_id, self.comma_id,
+        words, ln, steps, dev = _clean_rows(dec_seq_list, row, pad=self.pad, eos=self.eos, remove_dup=self.remove_dup)
+        counts = ops.caption_ngram_counts(words, ln, self._vid_off(steps, dev), self.V, self.period_id, self.comma_id,
                                           vocab_bits=self.vocab_bits, steps=steps)
         ops.decode_metric_accum(counts, self.acc)
         self.last_counts, self.last_clean = counts, (words, ln)
@@ -170,9 +178,7 @@ class IngredientF1:
 
     def __init__(self, lexicon):
         self.lexicon = lexicon
-        self.device = torch.device(lexicon.device)
-        if self.device.type != "cuda":
-            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.device = _gpu_device(lexicon.device)
         self.acc = torch.zeros(3, dtype=torch.int64, device=self.device)
         self.last_masks = self.last_extra = self.last_counts = None
 
@@ -185,16 +191,7 @@ class IngredientF1:
             raise ValueError("the plan was made by another lexicon")
         if not plan.has_gt:
             raise ValueError("IngredientF1 needs the ground-truth sentences of every video (gt_sentences in lexicon.plan)")
-        ids, steps = ops.stack_captions(dec_seq_list)
-        lt = ids.shape[-1]
-        ops.check_caption_metrics(lt, ids.dtype, steps=steps, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
-        if not ids.is_cuda:
-            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
-        if clean is None:
-            clean = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
-        words, ln = clean
-        if tuple(words.shape) != (ids.shape[0], lt):
-            raise ValueError("clean=(words, len) must be the clean-up of these %d rows of %d positions" % (ids.shape[0], lt))
+        words, ln, steps, _ = _clean_rows(dec_seq_list, row, clean)
         masks, extra, _, counts = ops.caption_ingredients(words, ln, plan, self.acc, steps=steps)
         self.last_masks, self.last_extra, self.last_counts = masks, extra, counts
         return counts
@@ -228,9 +225,7 @@ class CaptionScores:
 
     def __init__(self, corpus):
         self.corpus = corpus
-        self.device = torch.device(corpus.device)
-        if self.device.type != "cuda":
-            raise _lib.SvpcKernelError("svpc_amd.metrics: counters live on the GPU (no CPU fallback)")
+        self.device = _gpu_device(corpus.device)
         self.state = torch.zeros(13 + corpus.n_docs, dtype=torch.int64, device=self.device)
         self.acc_i, self.acc_f, self.seen = self.state[:11], self.state[11:13].view(torch.float64), self.state[13:]
         self.last_counts = self.last_scores = None
@@ -242,16 +237,7 @@ class CaptionScores:
     def update(self, dec_seq_list, plan, row=0, clean=None):
         if plan.corpus is not self.corpus:
             raise ValueError("the plan was made by another reference corpus")
-        ids, steps = ops.stack_captions(dec_seq_list)
-        lt = ids.shape[-1]
-        ops.check_caption_metrics(lt, ids.dtype, k=ids.shape[1] if ids.dim() == 3 else None, row=row)
-        if not ids.is_cuda:
-            raise _lib.SvpcKernelError("svpc_amd.metrics: captions must be on the GPU (no CPU fallback)")
-        if clean is None:
-            clean = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
-        words, ln = clean
-        if tuple(words.shape) != (ids.shape[0], lt):
-            raise ValueError("clean=(words, len) must be the clean-up of these %d rows of %d positions" % (ids.shape[0], lt))
+        words, ln, steps, _ = _clean_rows(dec_seq_list, row, clean, video_cap=False)          # (its cap is plan.check_cap, in caption_tokens)
         tokens, tok_len = ops.caption_tokens(words, ln, plan, steps)
         counts, scores = ops.caption_score_counts(tokens, tok_len, plan, seen=self.seen)
         ops.caption_score_accum(counts, scores, self.acc_i, self.acc_f)

@@ -2852,6 +2852,33 @@ def check_caption_metrics(lt, ids_dtype=None, steps=None, k=None, row=None, peri
     return r, (_NO_ID if period_id is None else int(period_id)), (_NO_ID if comma_id is None else int(comma_id))
 
 
+def _clean_pair(fn, words, length):
+    """``words`` (T, Lt) / ``length`` (T,) are contiguous int32 as ``clean_captions`` returns them → (T, Lt)"""
+    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
+        raise ValueError("%s: words must be contiguous int32 (T, Lt)" % fn)
+    T, lt = words.shape
+    if not _row_vec(length, T, torch.int32):
+        raise ValueError("%s: len must be contiguous int32 (T,)" % fn)
+    return T, lt
+
+
+def _plan_rows(fn, plan, steps, T, signed=False):
+    """``steps`` gives the plan's videos' row counts and they add up to T (``signed``: a negative count passes here)"""
+    if len(steps) != plan.n_vid or sum(steps) != T or (not signed and any(s < 0 for s in steps)):
+        raise ValueError("%s: the plan's %d video(s) with rows %r do not add up to T = %d" % (fn, plan.n_vid, steps, T))
+
+
+def _plan_device(fn, plan, t, what):
+    if plan.buf.device != t.device:
+        raise ValueError("%s: the plan lives on %s, the %s on %s" % (fn, plan.buf.device, what, t.device))
+
+
+def _accumulator(fn, name, acc, dtype, n, like, what):
+    """``acc`` is a contiguous tensor of ``n`` elements of ``dtype`` on the device of ``like`` (the caller's ``what``)"""
+    if acc.dtype != dtype or acc.numel() != n or not acc.is_contiguous() or acc.device != like.device:
+        raise ValueError("%s: %s must be a contiguous %s (%d,) tensor on the %s' device" % (fn, name, str(dtype)[6:], n, what))
+
+
 def clean_captions(ids, pad, eos, ignore=-1, remove_dup=True, row=None):
     """The captions the reference submits, from decoded ids (svpc_caption_clean): ``ids`` (T, Lt) or (T, K, Lt) int64 / int32 (``row``
     picks one of the K rows per sentence, default 0) → (words (T, Lt) int32: the ids without ``pad`` / ``ignore``, without the first of
@@ -2877,11 +2904,7 @@ def caption_ngram_counts(words, length, vid_off, V, period_id=None, comma_id=Non
     counts (N, 12) int32: total_1..4, distinct_1..4, n_sen, n_words, n_empty, n_copied.  ``vocab_bits``: an int32 device bitmap of
     ≥ ⌈V / 32⌉ words that collects the ids < V seen.  ``steps``: the videos' row counts when the caller knows them (a device ``vid_off``
     is not read back to check the 4096-position cap)."""
-    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
-        raise ValueError("caption_ngram_counts: words must be contiguous int32 (T, Lt)")
-    T, lt = words.shape
-    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
-        raise ValueError("caption_ngram_counts: len must be contiguous int32 (T,)")
+    T, lt = _clean_pair("caption_ngram_counts", words, length)
     if not torch.is_tensor(vid_off):
         off = [int(v) for v in vid_off]
         if steps is None:
@@ -2912,8 +2935,7 @@ def decode_metric_accum(counts, acc):
     svpc_decode_metric_accum (fixed summation order)."""
     if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != CAPTION_COUNT_COLS or not counts.is_contiguous():
         raise ValueError("decode_metric_accum: counts must be contiguous int32 (N, %d)" % CAPTION_COUNT_COLS)
-    if acc.dtype != torch.float64 or acc.numel() != 13 or not acc.is_contiguous() or acc.device != counts.device:
-        raise ValueError("decode_metric_accum: acc must be a contiguous float64 (13,) tensor on the counts' device")
+    _accumulator("decode_metric_accum", "acc", acc, torch.float64, 13, counts, "counts")
     _need_gpu(counts)
     _lib.call("decode_metric_accum", _p(counts), counts.shape[0], _p(acc), _stream())
     return acc
@@ -2956,19 +2978,13 @@ def caption_ingredients(words, length, plan, acc=None, steps=None):
     (masks (T,) int64: bit e = listed ingredient e of the row's video is mentioned; extra (T,) int32 extra words;
     row_counts (T, 3) int32 = correct, len(generated list), len(ground-truth list), zeros for a row without a ground-truth step;
     vid_counts (N, 3) int32 their sums per video).  Two launches, nothing uploaded for a recurring (S_b) structure."""
-    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
-        raise ValueError("caption_ingredients: words must be contiguous int32 (T, Lt)")
-    T, lt = words.shape
-    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
-        raise ValueError("caption_ingredients: len must be contiguous int32 (T,)")
+    T, lt = _clean_pair("caption_ingredients", words, length)
     check_caption_metrics(lt)
     steps = plan.default_steps() if steps is None else [int(s) for s in steps]
-    if len(steps) != plan.n_vid or sum(steps) != T:
-        raise ValueError("caption_ingredients: the plan's %d video(s) with rows %r do not add up to T = %d" % (plan.n_vid, steps, T))
-    if plan.buf.device != words.device:
-        raise ValueError("caption_ingredients: the plan lives on %s, the captions on %s" % (plan.buf.device, words.device))
-    if acc is not None and (acc.dtype != torch.int64 or acc.numel() != 3 or not acc.is_contiguous() or acc.device != words.device):
-        raise ValueError("caption_ingredients: acc must be a contiguous int64 (3,) tensor on the captions' device")
+    _plan_rows("caption_ingredients", plan, steps, T, signed=True)          # (a negative count is plan.rows' error, below)
+    _plan_device("caption_ingredients", plan, words, "captions")
+    if acc is not None:
+        _accumulator("caption_ingredients", "acc", acc, torch.int64, 3, words, "captions")
     _need_gpu(words)
     rows = plan.rows(steps)
     lex, N = plan.lexicon, plan.n_vid
@@ -2994,18 +3010,12 @@ def caption_tokens(words, length, plan, steps):
     ``clean_captions`` returns them (run collapse on), ``plan`` a ``caption_scores.ScorePlan``, ``steps`` the videos' row counts →
     (tokens (N, 1024) int32 lexicon ids, zero past the end; tok_len (N,) int32).  ValueError when a video's hypothesis could exceed 1,024
     tokens (S_b · (Lt − 1) · the longest expansion of a word)."""
-    if words.dim() != 2 or words.dtype != torch.int32 or not words.is_contiguous():
-        raise ValueError("caption_tokens: words must be contiguous int32 (T, Lt)")
-    T, lt = words.shape
-    if length.dtype != torch.int32 or tuple(length.shape) != (T,) or not length.is_contiguous():
-        raise ValueError("caption_tokens: len must be contiguous int32 (T,)")
+    T, lt = _clean_pair("caption_tokens", words, length)
     steps = [int(s) for s in steps]
     check_caption_metrics(lt)
-    if len(steps) != plan.n_vid or sum(steps) != T or any(s < 0 for s in steps):
-        raise ValueError("caption_tokens: the plan's %d video(s) with rows %r do not add up to T = %d" % (plan.n_vid, steps, T))
+    _plan_rows("caption_tokens", plan, steps, T)
     plan.check_cap(steps, lt)
-    if plan.buf.device != words.device:
-        raise ValueError("caption_tokens: the plan lives on %s, the captions on %s" % (plan.buf.device, words.device))
+    _plan_device("caption_tokens", plan, words, "captions")
     _need_gpu(words)
     cp, N = plan.corpus, plan.n_vid
     vid_off = plan.vid_off(steps)
@@ -3028,11 +3038,10 @@ def caption_score_counts(tokens, tok_len, plan, seen=None):
         raise ValueError("caption_score_counts: tokens must be contiguous int32 (%d, %d)" % (N, CAPTION_TOKENS))
     if tok_len.dtype != torch.int32 or tuple(tok_len.shape) != (N,) or not tok_len.is_contiguous():
         raise ValueError("caption_score_counts: tok_len must be contiguous int32 (%d,)" % N)
-    if plan.buf.device != tokens.device:
-        raise ValueError("caption_score_counts: the plan lives on %s, the tokens on %s" % (plan.buf.device, tokens.device))
+    _plan_device("caption_score_counts", plan, tokens, "tokens")
     cp = plan.corpus
-    if seen is not None and (seen.dtype != torch.int64 or seen.numel() != cp.n_docs or not seen.is_contiguous() or seen.device != tokens.device):
-        raise ValueError("caption_score_counts: seen must be a contiguous int64 (%d,) tensor on the tokens' device" % cp.n_docs)
+    if seen is not None:
+        _accumulator("caption_score_counts", "seen", seen, torch.int64, cp.n_docs, tokens, "tokens")
     _need_gpu(tokens)
     counts = torch.empty(N, CAPTION_SCORE_COUNT_COLS, dtype=torch.int32, device=tokens.device)
     scores = torch.empty(N, CAPTION_SCORE_COLS, dtype=torch.float64, device=tokens.device)
@@ -3049,10 +3058,8 @@ def caption_score_accum(counts, scores, acc_i, acc_f):
         raise ValueError("caption_score_accum: counts must be contiguous int32 (N, %d)" % CAPTION_SCORE_COUNT_COLS)
     if scores.dtype != torch.float64 or tuple(scores.shape) != (counts.shape[0], CAPTION_SCORE_COLS) or not scores.is_contiguous():
         raise ValueError("caption_score_accum: scores must be contiguous float64 (N, %d)" % CAPTION_SCORE_COLS)
-    if acc_i.dtype != torch.int64 or acc_i.numel() != 11 or not acc_i.is_contiguous() or acc_i.device != counts.device:
-        raise ValueError("caption_score_accum: acc_i must be a contiguous int64 (11,) tensor on the counts' device")
-    if acc_f.dtype != torch.float64 or acc_f.numel() != 2 or not acc_f.is_contiguous() or acc_f.device != counts.device:
-        raise ValueError("caption_score_accum: acc_f must be a contiguous float64 (2,) tensor on the counts' device")
+    _accumulator("caption_score_accum", "acc_i", acc_i, torch.int64, 11, counts, "counts")
+    _accumulator("caption_score_accum", "acc_f", acc_f, torch.float64, 2, counts, "counts")
     _need_gpu(counts)
     _lib.call("caption_score_accum", _p(counts), _p(scores), counts.shape[0], _p(acc_i), _p(acc_f), _stream())
     return acc_i, acc_f

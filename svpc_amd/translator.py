@@ -357,43 +357,42 @@ class Translator(object):
         return self._translate(model_inputs, self.model, decode=Decode(SAMPLE, R, n_best=R, seed=s["seed"], sampling=tuple(
             s[k] for k in ("random_sampling_temp", "random_sampling_topk", "random_sampling_topp", "min_length"))))
 
+    @staticmethod
+    def _clean(dec_seq_list, row, remove_dup=True):
+        """→ (words (T, Lt), len (T,)) int32 of the stacked decode, and the videos' row counts"""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        return ops.clean_captions(ids, PAD, EOS, IGNORE, remove_dup, row=row) + (steps,)
+
+    @staticmethod
+    def _per_video(t, steps):
+        """a (T, …) tensor as the videos' consecutive (S_b, …) views"""
+        offs = [0]
+        for s in steps:
+            offs.append(offs[-1] + s)
+        return [t[a:b] for a, b in zip(offs[:-1], offs[1:])]
+
     def clean_captions(self, dec_seq_list, row=0, remove_dup=True):
         """The captions the reference submits, on the device (``ops.clean_captions``): ``dec_seq_list`` as any
         ``translate_batch*`` returns it (per video (S_b, Lt), or (S_b, K, Lt) with ``row`` picking one of the K) →
         (clean_list, len_list): per video (S_b, Lt) int64 clean ids (PAD-filled) and (S_b,) int64 lengths, views of one buffer each.
         One launch for the batch when the list is what the translator returned; no host synchronisation."""
-        ids, steps = ops.stack_captions(dec_seq_list)
-        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, remove_dup, row=row)
-        words, ln = words.to(torch.int64), ln.to(torch.int64)
-        clean_list, len_list, o = [], [], 0
-        for s in steps:
-            clean_list.append(words[o:o + s])
-            len_list.append(ln[o:o + s])
-            o += s
-        return clean_list, len_list
+        words, ln, steps = self._clean(dec_seq_list, row, remove_dup)
+        return self._per_video(words.to(torch.int64), steps), self._per_video(ln.to(torch.int64), steps)
 
     def caption_ingredients(self, dec_seq_list, plan, row=0):
         """Which ingredients each decoded caption mentions (``ops.caption_ingredients``): ``dec_seq_list`` as any
         ``translate_batch*`` returns it, ``plan`` = ``IngredientLexicon.plan(videos)`` of the same videos → (mask_list, extra_list): per
         video (S_b,) int64 masks (bit e: listed ingredient e is mentioned; ``ingredients.masks_to_names`` gives the names) and (S_b,)
         int64 counts of the other known ingredient words, views of one buffer each.  No host synchronisation."""
-        ids, steps = ops.stack_captions(dec_seq_list)
-        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        words, ln, steps = self._clean(dec_seq_list, row)
         masks, extra, _, _ = ops.caption_ingredients(words, ln, plan, None, steps=steps)
-        extra = extra.to(torch.int64)
-        mask_list, extra_list, o = [], [], 0
-        for s in steps:
-            mask_list.append(masks[o:o + s])
-            extra_list.append(extra[o:o + s])
-            o += s
-        return mask_list, extra_list
+        return self._per_video(masks, steps), self._per_video(extra.to(torch.int64), steps)
 
     def caption_scores(self, dec_seq_list, plan, row=0):
         """Bleu_1…4, ROUGE_L and CIDEr of every video's decoded paragraph against its references (``ops.caption_score_counts``; DESIGN
         §11.6): ``dec_seq_list`` as any ``translate_batch*`` returns it, ``plan`` = ``ReferenceCorpus.plan(videos)`` of the same videos →
         (N, 6) float64 on the device, e.g. to rank n-best rows or samples.  No host synchronisation."""
-        ids, steps = ops.stack_captions(dec_seq_list)
-        words, ln = ops.clean_captions(ids, PAD, EOS, IGNORE, True, row=row)
+        words, ln, steps = self._clean(dec_seq_list, row)
         tokens, tok_len = ops.caption_tokens(words, ln, plan, steps)
         return ops.caption_score_counts(tokens, tok_len, plan)[1]
 

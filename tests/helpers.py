@@ -1,4 +1,7 @@
-"""Shared test helpers: build the product model from a golden fixture."""
+"""Shared test helpers: build the product model from a golden fixture; decoded-caption lists for the evaluation metrics' tests; the digests
+of the evaluation plans' device-facing tables."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -34,6 +37,47 @@ def build_model(case, mt, golden_dir, device="cpu"):
                                                               key=lambda s: int(s.split("/")[1]))]
     model.gumbel_noise = noise or None
     return z, cfg, batch, model
+
+
+def as_views(vids_rows, lt, dtype=torch.int64, device="cuda:0"):
+    """per-video lists of id rows → per-video (S_b, lt) tensors that are consecutive views of one device buffer (what a decode returns)"""
+    buf = torch.tensor([r for v in vids_rows for r in v], dtype=dtype, device=device).view(-1, lt)
+    out, o = [], 0
+    for v in vids_rows:
+        out.append(buf[o:o + len(v)])
+        o += len(v)
+    return out
+
+
+def host_rows(dec, row=None):
+    return [(d if row is None else d[:, row]).cpu().tolist() for d in dec]
+
+
+def _sha(t):
+    a = np.ascontiguousarray(t.numpy() if torch.is_tensor(t) else t)
+    return hashlib.sha256(("%s%s" % (a.dtype, a.shape)).encode() + a.tobytes()).hexdigest()
+
+
+def eval_plan_digests(golden_dir):
+    """SHA-256 (over dtype, shape and bytes) of every device-facing table the evaluation plans build on the CPU for the batches of
+    ingredient_f1.json and caption_scores.json, one lexicon / corpus each, batches planned in file order
+    (tests/golden/eval_plan_digests.json records them; tools/make_golden_eval_plan_digests.py)."""
+    from svpc_amd.caption_scores import ReferenceCorpus
+    from svpc_amd.ingredients import IngredientLexicon
+
+    def plan_digest(plan):
+        return dict(buf=_sha(plan.buf), sections=[[k, o, n] for k, (o, n) in plan.sections.items()])
+    g = json.load(open(os.path.join(golden_dir, "ingredient_f1.json")))
+    lex = IngredientLexicon(g["idx2word"], set(g["all_ingredients"]), device="cpu")
+    ingredient = dict(a_bits=_sha(lex.a_bits), batches=[])
+    for b in g["batches"]:
+        plan = lex.plan([dict(ingredients=v["ingredients"], oov_word_dict=v["oov"], gt_sentences=v["gt_sentences"]) for v in b["videos"]])
+        ingredient["batches"].append(dict(plan_digest(plan), n_rows=lex.n_rows, table=_sha(lex.table[:lex.n_rows])))
+    g = json.load(open(os.path.join(golden_dir, "caption_scores.json")))
+    corpus = ReferenceCorpus(g["idx2word"], g["references"], device="cpu")
+    scores = {k: _sha(getattr(corpus, k)) for k in ("voc_off", "voc_tok", "ref_tok", "tab_key", "tab_idf", "gauss")}
+    scores["batches"] = [plan_digest(corpus.plan([dict(key=v["key"], oov_word_dict=v["oov"]) for v in b["videos"]])) for b in g["batches"]]
+    return dict(ingredient_f1=ingredient, caption_scores=scores)
 
 
 def product_sources_sha16():

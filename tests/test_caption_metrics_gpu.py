@@ -15,7 +15,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import caption_metrics_reference as cm  # noqa: E402
-from helpers import build_model  # noqa: E402
+from helpers import as_views as _as_views, build_model, host_rows as _host_rows  # noqa: E402
 from svpc_amd import ops, synthetic as syn  # noqa: E402
 from svpc_amd.metrics import DecodeMetrics  # noqa: E402
 from svpc_amd.synthetic import BOS, EOS, IGNORE, PAD, UNK  # noqa: E402
@@ -192,15 +192,6 @@ def test_counts_at_the_word_cap():
 
 
 # ------------------------------------------------------------------------------------------------ 3. DecodeMetrics
-def _as_views(vids, lt, dtype=torch.int64):
-    buf = torch.tensor([r for v in vids for r in v], dtype=dtype, device=DEV).view(-1, lt)
-    out, o = [], 0
-    for v in vids:
-        out.append(buf[o:o + len(v)])
-        o += len(v)
-    return out
-
-
 def test_decode_metrics_against_the_restatement():
     rng = np.random.default_rng(8)
     lt = 22
@@ -276,10 +267,6 @@ def test_decode_metrics_update_captured():
 
 
 # ------------------------------------------------------------------------------------------------ 4. end to end
-def _host_rows(dec, row=None):
-    return [(d if row is None else d[:, row]).cpu().tolist() for d in dec]
-
-
 @pytest.mark.parametrize("case", ["tiny", "c1"])
 def test_decode_metrics_end_to_end(golden_dir, case):
     from svpc_amd.translator import Translator, ids_to_sentences

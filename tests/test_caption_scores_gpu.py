@@ -17,7 +17,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import caption_scores_reference as cs  # noqa: E402
-from helpers import build_model  # noqa: E402
+from helpers import as_views as _views, build_model, host_rows as _host_rows  # noqa: E402
 from svpc_amd import ops, synthetic as syn  # noqa: E402
 from svpc_amd.caption_scores import ReferenceCorpus  # noqa: E402
 from svpc_amd.metrics import CaptionScores, DecodeMetrics  # noqa: E402
@@ -97,15 +97,6 @@ def _rows(sentences, w2i, lt, oov=None):
         ids = [look[w] for w in (s.split(" ") if s else [])]
         assert len(ids) <= lt - 2
         out.append(([BOS] + ids + [EOS] + [PAD] * lt)[:lt])
-    return out
-
-
-def _views(vids_rows, lt, dtype=torch.int64):
-    buf = torch.tensor([r for v in vids_rows for r in v], dtype=dtype, device=DEV).view(-1, lt)
-    out, o = [], 0
-    for v in vids_rows:
-        out.append(buf[o:o + len(v)])
-        o += len(v)
     return out
 
 
@@ -375,10 +366,6 @@ def test_update_captured(gold):
 
 
 # ------------------------------------------------------------------------------------------------ 4. end to end
-def _host_rows(dec, row=None):
-    return [(d if row is None else d[:, row]).cpu().tolist() for d in dec]
-
-
 @pytest.mark.parametrize("case", ["tiny", "c1"])
 def test_caption_scores_end_to_end(golden_dir, case):
     from svpc_amd.translator import Translator

@@ -14,7 +14,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import ingredient_f1_reference as ir  # noqa: E402
-from helpers import build_model  # noqa: E402
+from helpers import as_views as _views, build_model, host_rows as _host_rows  # noqa: E402
 from svpc_amd import ops, synthetic as syn  # noqa: E402
 from svpc_amd.ingredients import IngredientLexicon, masks_to_names  # noqa: E402
 from svpc_amd.metrics import DecodeMetrics, IngredientF1  # noqa: E402
@@ -29,15 +29,6 @@ WORDS, A, V = GOLD["idx2word"], set(GOLD["all_ingredients"]), GOLD["V"]
 
 def _video(v):
     return dict(ingredients=v["ingredients"], oov_word_dict=v["oov"], gt_sentences=v["gt_sentences"])
-
-
-def _views(vids_rows, lt, dtype=torch.int64):
-    buf = torch.tensor([r for v in vids_rows for r in v], dtype=dtype, device=DEV).view(-1, lt)
-    out, o = [], 0
-    for v in vids_rows:
-        out.append(buf[o:o + len(v)])
-        o += len(v)
-    return out
 
 
 def _same(got, ref):
@@ -256,10 +247,6 @@ def test_update_captured(lexicon):
 
 
 # ------------------------------------------------------------------------------------------------ 3. end to end
-def _host_rows(dec, row=None):
-    return [(d if row is None else d[:, row]).cpu().tolist() for d in dec]
-
-
 @pytest.mark.parametrize("case", ["tiny", "c1"])
 def test_ingredient_f1_end_to_end(golden_dir, case):
     from svpc_amd.translator import Translator

@@ -13,58 +13,22 @@ of a decode_update batch that the update takes.  Prints one JSON line.
     python tools/bench_decode_metrics.py [--steps 10] [--warmup 2] [--rounds 4] [--videos 64] [--precision bf16x3] [--profile]
 
 With --profile only a few replayed decodes + updates run (for rocprofv3 --kernel-trace --stats)."""
-import argparse
 import json
-import os
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from eval_tail_bench import against_decode, alternate, arguments, config5, leg, run
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--videos", type=int, default=64)
-    ap.add_argument("--clips", type=int, default=12)
-    ap.add_argument("--precision", default="bf16x3", choices=["bf16", "bf16x3", "fp32"])
-    ap.add_argument("--profile", action="store_true")
-    a = ap.parse_args(argv)
+    a = arguments(argv, profile=True)
     import torch
-    import bench
     import caption_metrics_reference as cm
-    from svpc_amd import make_batch, ops, synthetic as syn
     from svpc_amd.metrics import DecodeMetrics
-    from svpc_amd.translator import Translator
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(0)
-    stream = torch.cuda.Stream(device=dev)
-    with torch.cuda.stream(stream):
-        ops.set_precision(a.precision)
-        args = bench.parse_args([])
-        cfg, model = bench.build(args, dev)
-        b = make_batch(cfg, n_videos=a.videos, max_steps=a.clips, n_ingr=10, n_oov=0, seed=2019, full_clips=True)
-        b["_ingr_host_lists"] = (b["ingr_input_ids"].tolist(), b["ingr_masks"].tolist(), b["ingr_sep_masks"].tolist())
-        for k, v in list(b.items()):
-            if isinstance(v, list) and v and isinstance(v[0], torch.Tensor):
-                b[k] = [t.to(dev) for t in v]
-            elif isinstance(v, torch.Tensor):
-                b[k] = v.to(dev)
-        O = type("O", (), {"cuda": True})
-        tr = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=True)
+    with config5(a) as (cfg, dev, b, decode):
         V = cfg.vocab_size
         period, comma = 9, 10                      # (the synthetic vocabulary has no punctuation: any two word ids exercise the rule)
         dm = DecodeMetrics(V, dev, period_id=period, comma_id=comma)
         host = {"videos": []}
-
-        def decode():
-            return tr.translate_batch(syn.translate_inputs(b))[0]
 
         def decode_update():
             dec = decode()
@@ -77,14 +41,6 @@ def main(argv=None):
             host["videos"] += vids
             return dec
 
-        def run(fn, steps):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            return time.perf_counter() - t0
-
         for _ in range(max(1, a.warmup)):              # eager warm-up + capture, then replays; the update's offsets table is cached
             decode_update()
         torch.cuda.synchronize()
@@ -92,12 +48,8 @@ def main(argv=None):
             run(decode_update, 3)
             print(json.dumps({"profiled": "three replayed decodes, each followed by DecodeMetrics.update", "videos": a.videos}))
             return
-        sent = a.videos * a.clips
         dm.reset()
-        times = {"decode": [], "decode_update": []}
-        for _ in range(a.rounds):
-            for name, fn in (("decode", decode), ("decode_update", decode_update)):
-                times[name].append(run(fn, a.steps))
+        times = alternate((("decode", decode), ("decode_update", decode_update)), a.rounds, a.steps)
         res = dm.result()                              # the epoch's single read-back
         t_host = []
         for _ in range(max(1, a.rounds // 2)):
@@ -116,20 +68,13 @@ def main(argv=None):
         one, ref = dm.result(), cm.epoch_result(host["videos"], V, period, comma)[0]
         same = all(one[k] == ref[k] for k in ("num_videos", "num_sen", "num_words", "num_empty", "num_copied", "vocab_size")) and all(
             abs(one[k] - ref[k]) <= 1e-12 for k in ("re1", "re2", "re3", "re4", "div1", "div2", "div3", "div4"))
-
-        def leg(ts):
-            return {"captions_per_s_best": sent * a.steps / min(ts), "captions_per_s_median": sent * a.steps / statistics.median(ts),
-                    "ms_per_batch_best": 1000.0 * min(ts) / a.steps, "ms_per_batch_median": 1000.0 * statistics.median(ts) / a.steps,
-                    "rounds": len(ts)}
-        legs = {"decode": leg(times["decode"]), "decode_update": leg(times["decode_update"]), "decode_host_tail": leg(t_host)}
+        legs = {"decode": leg(times["decode"], a), "decode_update": leg(times["decode_update"], a), "decode_host_tail": leg(t_host, a)}
         d, u, h = (legs[k] for k in ("decode", "decode_update", "decode_host_tail"))
         print(json.dumps({
             "metric": "greedy decode captions/sec with and without the evaluation tail (config 5)", "videos": a.videos, "clips": a.clips,
             "precision": a.precision, "launch": "hipGraph replay of the decode; DecodeMetrics.update eager (three launches)",
             "steps": a.steps, "order": "decode, decode_update alternating; decode_host_tail afterwards", "legs": legs,
-            "update_vs_decode_best": u["captions_per_s_best"] / d["captions_per_s_best"],
-            "update_vs_decode_median": u["captions_per_s_median"] / d["captions_per_s_median"],
-            "update_ms_per_batch": u["ms_per_batch_median"] - d["ms_per_batch_median"],
+            **against_decode("update", u, d),
             "update_share_of_batch": 1.0 - d["ms_per_batch_median"] / u["ms_per_batch_median"],
             "host_tail_vs_decode_best": h["captions_per_s_best"] / d["captions_per_s_best"],
             "host_tail_ms_per_batch": h["ms_per_batch_median"] - d["ms_per_batch_median"],

@@ -12,52 +12,19 @@ same words.  Each leg reports its best and median round.  ``f1_vs_decode`` = cap
 
     python tools/bench_ingredient_f1.py [--steps 10] [--warmup 2] [--rounds 4] [--videos 64] [--precision bf16x3]
 """
-import argparse
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from eval_tail_bench import against_decode, alternate, arguments, config5, leg
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--rounds", type=int, default=4)
-    ap.add_argument("--videos", type=int, default=64)
-    ap.add_argument("--clips", type=int, default=12)
-    ap.add_argument("--precision", default="bf16x3", choices=["bf16", "bf16x3", "fp32"])
-    a = ap.parse_args(argv)
+    a = arguments(argv)
     import numpy as np
     import torch
-    import bench
     import ingredient_f1_reference as ir
-    from svpc_amd import make_batch, ops, synthetic as syn
     from svpc_amd.ingredients import IngredientLexicon
     from svpc_amd.metrics import DecodeMetrics, IngredientF1
-    from svpc_amd.translator import Translator
-    dev = torch.device("cuda", 0)
-    torch.cuda.set_device(0)
-    stream = torch.cuda.Stream(device=dev)
-    with torch.cuda.stream(stream):
-        ops.set_precision(a.precision)
-        args = bench.parse_args([])
-        cfg, model = bench.build(args, dev)
-        b = make_batch(cfg, n_videos=a.videos, max_steps=a.clips, n_ingr=10, n_oov=0, seed=2019, full_clips=True)
-        b["_ingr_host_lists"] = (b["ingr_input_ids"].tolist(), b["ingr_masks"].tolist(), b["ingr_sep_masks"].tolist())
-        for k, v in list(b.items()):
-            if isinstance(v, list) and v and isinstance(v[0], torch.Tensor):
-                b[k] = [t.to(dev) for t in v]
-            elif isinstance(v, torch.Tensor):
-                b[k] = v.to(dev)
-        O = type("O", (), {"cuda": True})
-        tr = Translator(O(), {"model_cfg": cfg, "model": model.state_dict()}, model=model, graph=True)
+    with config5(a) as (cfg, dev, b, decode):
         V = cfg.vocab_size
         i2w = ["w%d" % i for i in range(V)]
         rng = np.random.default_rng(2019)
@@ -75,9 +42,6 @@ def main(argv=None):
         f1 = IngredientF1(lex)
         dm = DecodeMetrics(V, dev)
 
-        def decode():
-            return tr.translate_batch(syn.translate_inputs(b))[0]
-
         def decode_f1():
             dec = decode()
             f1.update(dec, plan)
@@ -89,25 +53,13 @@ def main(argv=None):
             f1.update(dec, plan, clean=dm.last_clean)
             return dec
 
-        def run(fn, steps):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                fn()
-            torch.cuda.synchronize()
-            return time.perf_counter() - t0
-
         for _ in range(max(1, a.warmup)):              # eager warm-up + capture, then replays; the updates' tables are cached
             decode_f1()
             decode_metrics_f1()
         torch.cuda.synchronize()
-        sent = a.videos * a.clips
         f1.reset()
         legs_fn = (("decode", decode), ("decode_f1", decode_f1), ("decode_metrics_f1", decode_metrics_f1))
-        times = {k: [] for k, _ in legs_fn}
-        for _ in range(a.rounds):
-            for name, fn in legs_fn:
-                times[name].append(run(fn, a.steps))
+        times = alternate(legs_fn, a.rounds, a.steps)
         res = f1.result()                              # the epoch's single read-back
         # one batch through the device and through the Python statement: the same totals
         f1.reset()
@@ -116,23 +68,13 @@ def main(argv=None):
         ref, _ = ir.epoch_result([[(d.cpu().tolist(), v) for d, v in zip(dec, videos)]], i2w, all_ingredients)
         same = all(one[k] == ref[k] for k in ("n_correct", "n_recall", "n_precision")) and all(
             abs(one[k] - ref[k]) <= 1e-12 for k in ("recall", "precision", "f1"))
-
-        def leg(ts):
-            return {"captions_per_s_best": sent * a.steps / min(ts), "captions_per_s_median": sent * a.steps / statistics.median(ts),
-                    "ms_per_batch_best": 1000.0 * min(ts) / a.steps, "ms_per_batch_median": 1000.0 * statistics.median(ts) / a.steps,
-                    "rounds": len(ts)}
-        legs = {k: leg(v) for k, v in times.items()}
+        legs = {k: leg(v, a) for k, v in times.items()}
         d, u, m = (legs[k] for k in ("decode", "decode_f1", "decode_metrics_f1"))
         print(json.dumps({
             "metric": "greedy decode captions/sec with and without the ingredient-F1 tail (config 5)", "videos": a.videos, "clips": a.clips,
             "precision": a.precision, "launch": "hipGraph replay of the decode; the updates eager", "steps": a.steps,
             "order": "decode, decode_f1, decode_metrics_f1 (one shared clean-up) alternating", "legs": legs,
-            "f1_vs_decode_best": u["captions_per_s_best"] / d["captions_per_s_best"],
-            "f1_vs_decode_median": u["captions_per_s_median"] / d["captions_per_s_median"],
-            "f1_ms_per_batch": u["ms_per_batch_median"] - d["ms_per_batch_median"],
-            "metrics_f1_vs_decode_best": m["captions_per_s_best"] / d["captions_per_s_best"],
-            "metrics_f1_vs_decode_median": m["captions_per_s_median"] / d["captions_per_s_median"],
-            "metrics_f1_ms_per_batch": m["ms_per_batch_median"] - d["ms_per_batch_median"],
+            **against_decode("f1", u, d), **against_decode("metrics_f1", m, d),
             "predicate_rows": lex.n_rows, "pattern_tokens_per_video_max": max(sum(len(n.split(" ")) for n in v["ingredients"]) for v in videos),
             "device_result_equals_python_statement": bool(same),
             "result": {k: res[k] for k in ("recall", "precision", "f1", "n_correct", "n_recall", "n_precision")}}))
