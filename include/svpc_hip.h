@@ -605,6 +605,30 @@ int svpc_caption_score_counts(const int* tokens, const int* tok_len, int n_vid, 
  * ROUGE_L, sum of CIDEr over the n_vid rows (a thread's rows in index order, then a fixed tree: deterministic); rows of -1 are left out. */
 int svpc_caption_score_accum(const int* counts, const double* scores, int n_vid, unsigned long long* acc_i, double* acc_f,
                              svpc_stream_t stream);
+/* ---- consensus (minimum Bayes risk) selection among the K <= 16 decoded candidates of a group: candidate i's utility against
+ *      candidate j is the six scores above with i as the hypothesis and j as the single reference, j's length and CIDEr norms computed on
+ *      the device by the same formulas (ROUGE_L against an empty j is 0); tokens, gram keys and the gram -> idf table as above.
+ * svpc_consensus_tokens: stream s = the clean rows first, first + stride, …, first + (rows - 1) * stride of words / len (n_rows rows, as
+ * svpc_caption_clean writes them) with streams (n_streams, 4) int32 = {first, rows, stride, video}; the video's row of vid (n_vid, 12)
+ * gives its copied words.  Out: tokens (n_streams, 1024) 16-bit (zero past the end), tok_len (n_streams,) — -1 over 1024 tokens. */
+int svpc_consensus_tokens(const int* words, const int* len, long long n_rows, const int* streams, int n_streams, int lt, int vocab,
+                          const int* voc_off, const int* voc_tok, int n_voc_tok, const int* vid, int n_vid, const int* oov_off, int n_oov_off,
+                          const int* oov_tok, int n_oov_tok, unsigned short* tokens, int* tok_len, svpc_stream_t stream);
+/* group g = the streams g * k … g * k + k - 1.  out (n_grp, k, k, 6) fp64: out[g][i][j] = Bleu_1..4, ROUGE_L, CIDEr of hypothesis i against
+ * the reference j, for every ordered pair, i = j included; every fp64 sum in a fixed order (the same inputs give the same bits).  A pair
+ * with a stream whose tok_len is -1: zeros.  work: n_grp * k * 4 doubles of the caller's (the candidates' squared norms between the two
+ * launches: one workgroup per (group, hypothesis), then one thread per pair). */
+int svpc_consensus_pair_scores(const unsigned short* tokens, const int* tok_len, int n_grp, int k, const unsigned long long* tab_key,
+                               const double* tab_idf, int tab_cap, double log_docs, const double* gauss, double* out, double* work,
+                               svpc_stream_t stream);
+/* per group g (its sentences are the rows grp_off[g] … grp_off[g + 1] - 1 of the n_rows): expected[g][i] = sum over j != i (ascending) of
+ * w_j * pair[g][i][j][col] / sum of w_j (0 when that is 0), fp64; w_j = 1, or with posterior != 0 exp(c_j - max c), c_j the fp64 sum over the
+ * group's rows in order of scores (n_rows, k) fp32 (all weights 1 when the maximum is -inf); pick[g] = the arg max, ties to the lowest i.
+ * With out_ids: for every row r of the group out_ids[r] = the lt ids of row pick of ids (n_rows, k, lt) (int64 when ids64, else int32),
+ * row_pick[r] = pick, and out_scores[r] / out_len[r] (or NULL) the chosen entries of scores / lengths (n_rows, k). */
+int svpc_consensus_pick(const double* pair, int n_grp, int k, int col, int posterior, const float* scores, const int* grp_off,
+                        long long n_rows, const void* ids, int ids64, int lt, const long long* lengths, int* pick, double* expected,
+                        long long* out_ids, long long* row_pick, float* out_scores, long long* out_len, svpc_stream_t stream);
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

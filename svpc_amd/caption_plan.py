@@ -5,6 +5,7 @@ captured.  One statement each of
 - ``Bounded``: the caches' bound (a dict emptied before the insertion that would outgrow it);
 - ``PackedTables``: named numpy sections → one int32 buffer, one upload; ``section`` / ``ptr`` / ``size`` by name;
 - ``RowTables``: the cached table of a decode's (S_b) structure — the videos' first rows, optionally (video, step) of every row;
+- ``GroupTables``: the cached tables of consensus selection's groups per (S_b structure, K, scope) (DESIGN §11.7);
 - ``vocabulary`` and ``copied_words``: the rules for ``idx2word`` and for a video's ``oov_word_dict`` (ids V … V + 127, each once);
 - ``PlanCompiler``: per-video compilation and per-batch plans, both cached by key.
 """
@@ -83,6 +84,39 @@ class RowTables(Bounded):
                 off.append(off[-1] + s)
             vs = [x for b, s in enumerate(steps) for i in range(s) for x in (b, i)] if self.rows else []
             t = self.put(key, torch.tensor(off + vs, dtype=torch.int32, device=device))
+        return t
+
+
+class GroupTables(Bounded):
+    """((S_b) structure, K, scope) → the int32 device table of consensus selection's groups: [streams (G · K, 4) = first
+    clean row, rows, row stride, video of stream g · K + k | grp_off (G + 1) first sentence of every group].  The clean rows are those of
+    the (T, K, Lt) decode taken as T · K rows, so candidate k of sentence t is row t · K + k.  ``paragraph``: one group per video,
+    candidate k is row k of each of its sentences in order; ``sentence``: one group per sentence.  Uploaded once per key and device."""
+
+    def __init__(self):
+        super().__init__(32)
+
+    def table(self, steps, k, scope, device, n_vid=None):
+        """→ (table, G); ValueError for row counts that do not describe ``n_vid`` videos"""
+        steps, k = tuple(int(s) for s in steps), int(k)
+        if n_vid is not None and (len(steps) != n_vid or any(s < 0 for s in steps)):
+            raise ValueError("the plan holds %d video(s), got the row counts %r" % (n_vid, list(steps)))
+        key = (steps, k, scope, str(device))
+        t = self.get(key)
+        if t is None:
+            streams, off, row0 = [], [0], 0
+            for b, s in enumerate(steps):
+                if scope == "paragraph":
+                    for c in range(k):
+                        streams += [row0 * k + c, s, k, b]
+                    off.append(row0 + s)
+                else:
+                    for r in range(row0, row0 + s):
+                        for c in range(k):
+                            streams += [r * k + c, 1, k, b]
+                        off.append(r + 1)
+                row0 += s
+            t = self.put(key, (torch.tensor(streams + off, dtype=torch.int32, device=device), len(off) - 1))
         return t
 
 

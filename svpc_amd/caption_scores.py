@@ -26,7 +26,7 @@ import re
 import numpy as np
 import torch
 
-from .caption_plan import CAP_COPIED, PackedTables, PlanCompiler, RowTables, copied_words, vocabulary
+from .caption_plan import CAP_COPIED, Bounded, GroupTables, PackedTables, PlanCompiler, RowTables, copied_words, vocabulary
 from .ingredients import ascii_word
 
 CAP_TOKENS = 1024           # tokens of a hypothesis and of a reference: both sit in the workgroup's LDS
@@ -78,7 +78,7 @@ class ScorePlan(PackedTables):
         vid, oov_off, oov_tok = [], [], []
         for b, c in enumerate(compiled):
             i = c["index"]
-            refs = corpus.ref_slots[i]
+            refs = corpus.ref_slots[i] if i >= 0 else []          # (a reference-free plan: n_ref = 0, index −1)
             row = [len(refs), i, len(c["tokens"]), len(oov_off)] + [0] * (VID_COLS - 4)
             for r, (off, n, nrm) in enumerate(refs):
                 row[4 + r], row[8 + r] = off, n
@@ -91,9 +91,14 @@ class ScorePlan(PackedTables):
         super().__init__(dict(ref_norm=norms, vid=np.array(vid, dtype=np.int32), oov_off=np.array(oov_off, dtype=np.int32),
                               oov_tok=np.array(oov_tok + [0], dtype=np.int32)), device)        # (the float64 section comes first)
         self._offs = RowTables()
+        self._groups = GroupTables()
 
     def vid_off(self, steps):
         return self._offs.table(steps, self.device, self.n_vid)
+
+    def groups(self, steps, k, scope):
+        """consensus selection's group tables of a decode's (S_b) structure with K candidates, cached → (table, G)"""
+        return self._groups.table(steps, k, scope, self.device, self.n_vid)
 
     def check_cap(self, steps, lt):
         """ValueError when a video's hypothesis could exceed 1,024 tokens: S_b · (Lt − 1) · (longest expansion of a word)"""
@@ -115,6 +120,7 @@ class ReferenceCorpus(PlanCompiler):
 
     def __init__(self, idx2word, references, device="cuda", table_capacity=None):
         super().__init__(device)
+        self._free_videos, self._free_plans = Bounded(4096), Bounded(32)
         idx2word = vocabulary(idx2word)
         if not len(references):
             raise ValueError("no references")
@@ -236,12 +242,35 @@ class ReferenceCorpus(PlanCompiler):
     def _compile(self, video):
         if video["key"] not in self.index_of:
             raise ValueError("video %r is not in the reference set" % (video["key"],))
+        return dict(self._copied(video), index=self.index_of[video["key"]])
+
+    def _copied(self, video):
         tokens = copied_words(video.get("oov_word_dict"), self.V, lambda w: [self._token_id(t) for t in parse_sent(ascii_word(w))],
                               missing=[])                                 # (an id no word of the video spells gives no token)
-        return dict(index=self.index_of[video["key"]], tokens=tokens, expansion=max([1] + [len(t) for t in tokens]))
+        return dict(tokens=tokens, expansion=max([1] + [len(t) for t in tokens]))
 
     def _plan(self, compiled):
         return ScorePlan(self, compiled, self.device)
+
+    def plan(self, videos, references=True):
+        """``references=False``: the plan of videos that have no references — the same packed layout with n_ref = 0 and index −1, any
+        ``key`` (or none) accepted — for consensus selection, where this corpus only supplies the vocabulary and the
+        idf.  Cached apart from the plans with references."""
+        if references:
+            return super().plan(videos)
+        if not len(videos):
+            raise ValueError("no videos to plan")
+        keys = tuple(tuple(sorted((v.get("oov_word_dict") or {}).items())) for v in videos)
+        p = self._free_plans.get(keys)
+        if p is None:
+            compiled = []
+            for v, k in zip(videos, keys):
+                c = self._free_videos.get(k)
+                if c is None:
+                    c = self._free_videos.put(k, dict(self._copied(v), index=-1))
+                compiled.append(c)
+            p = self._free_plans.put(keys, self._plan(compiled))
+        return p
 
 
 def bleu_from_totals(correct, guess, testlen, reflen):

@@ -3063,3 +3063,104 @@ def caption_score_accum(counts, scores, acc_i, acc_f):
     _need_gpu(counts)
     _lib.call("caption_score_accum", _p(counts), _p(scores), counts.shape[0], _p(acc_i), _p(acc_f), _stream())
     return acc_i, acc_f
+
+
+CONSENSUS_MAX = 16              # candidates of one group: their token streams (≤ 16 · 1,028 16-bit tokens) sit in the workgroup's LDS
+CONSENSUS_UTILITIES = ("Bleu_1", "Bleu_2", "Bleu_3", "Bleu_4", "ROUGE_L", "CIDEr")
+CONSENSUS_SCOPES = ("paragraph", "sentence")
+CONSENSUS_WEIGHTS = ("uniform", "posterior")
+
+
+def check_consensus(k=None, utility="CIDEr", scope="paragraph", weights="uniform", scores=True):
+    """Host checks of consensus selection (ValueError): 1 ≤ ``k`` ≤ 16 candidates, ``utility`` one of the six score
+    columns, ``scope`` "paragraph" or "sentence", ``weights`` "uniform" or "posterior" (which needs the candidates' ``scores``) →
+    the utility's column."""
+    if k is not None and (isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= CONSENSUS_MAX):
+        raise ValueError("consensus selection takes 1..%d candidates, got K = %r" % (CONSENSUS_MAX, k))
+    if utility not in CONSENSUS_UTILITIES:
+        raise ValueError("utility must be one of %s, got %r" % (", ".join(CONSENSUS_UTILITIES), utility))
+    if scope not in CONSENSUS_SCOPES:
+        raise ValueError("scope must be one of %s, got %r" % (", ".join(CONSENSUS_SCOPES), scope))
+    if weights not in CONSENSUS_WEIGHTS:
+        raise ValueError("weights must be one of %s, got %r" % (", ".join(CONSENSUS_WEIGHTS), weights))
+    if weights == "posterior" and scores is None:
+        raise ValueError("weights=\"posterior\" needs the candidates' scores")
+    return CONSENSUS_UTILITIES.index(utility)
+
+
+def _candidates(fn, ids, plan, steps):
+    """``ids`` is a decode's stacked (T, K, Lt) result of the plan's videos → (T, K, Lt, steps)"""
+    if ids.dim() != 3:
+        raise ValueError("%s: ids must be (T, K, Lt), got %s" % (fn, tuple(ids.shape)))
+    T, K, lt = ids.shape
+    check_consensus(K)
+    check_caption_metrics(lt, ids.dtype)
+    steps = [int(s) for s in steps]
+    _plan_rows(fn, plan, steps, T)
+    _plan_device(fn, plan, ids, "ids")
+    return T, K, lt, steps
+
+
+def consensus_pair_scores(ids, plan, steps, pad, eos, ignore=-1, scope="paragraph"):
+    """Every candidate of a group scored against every other (svpc_caption_clean over the T · K rows, svpc_consensus_tokens,
+    svpc_consensus_pair_scores: four launches whatever N and K): ``ids`` (T, K, Lt) int64 / int32 as
+    ``translate_batch_sample`` / ``translate_batch_nbest`` return them (stacked; cleaned as ``clean_captions`` does with ``pad`` /
+    ``eos`` / ``ignore``, run collapse on), ``plan`` a ``ScorePlan`` of the same videos (with or without references: only its copied
+    words and its corpus's idf are used), ``steps`` the videos' row counts.  ``scope``:
+    "paragraph" — one group per video, candidate k is row k of all its sentences; "sentence" — one group per sentence →
+    (pair (G, K, K, 6) float64: pair[g, i, j] = Bleu_1..4, ROUGE_L, CIDEr of candidate i against the single reference j;
+    tok_len (G, K) int32).  ValueError when a candidate's stream could exceed 1,024 tokens."""
+    T, K, lt, steps = _candidates("consensus_pair_scores", ids, plan, steps)
+    check_consensus(K, scope=scope)
+    plan.check_cap(steps if scope == "paragraph" else [min(s, 1) for s in steps], lt)
+    _need_gpu(ids)
+    ids = _c(ids)
+    dev = ids.device
+    table, G = plan.groups(steps, K, scope)
+    cp = plan.corpus
+    words = torch.empty(T * K, lt, dtype=torch.int32, device=dev)
+    ln = torch.empty(T * K, dtype=torch.int32, device=dev)
+    tokens = torch.empty(G * K, CAPTION_TOKENS, dtype=torch.int16, device=dev)
+    tok_len = torch.empty(G, K, dtype=torch.int32, device=dev)
+    pair = torch.empty(G, K, K, CAPTION_SCORE_COLS, dtype=torch.float64, device=dev)
+    work = torch.empty(G, K, 4, dtype=torch.float64, device=dev)                   # the candidates' squared CIDEr norms
+    if T:
+        _lib.call("caption_clean", _p(ids), 1 if ids.dtype == torch.int64 else 0, lt, 1, 0, T * K, lt, int(pad), int(eos), int(ignore), 1,
+                  _p(words), _p(ln), _stream())             # the (T, K, Lt) ids as T · K rows
+    _lib.call("consensus_tokens", _p(words), _p(ln), T * K, _p(table), G * K, lt, cp.V, _p(cp.voc_off), _p(cp.voc_tok), cp.voc_tok.numel(),
+              plan.ptr("vid"), plan.n_vid, plan.ptr("oov_off"), plan.size("oov_off"), plan.ptr("oov_tok"), plan.size("oov_tok"), _p(tokens),
+              _p(tok_len), _stream())
+    _lib.call("consensus_pair_scores", _p(tokens), _p(tok_len), G, K, _p(cp.tab_key), _p(cp.tab_idf), cp.table_capacity, cp.log_docs,
+              _p(cp.gauss), _p(pair), _p(work), _stream())
+    return pair, tok_len
+
+
+def consensus_pick(pair, ids, plan, steps, utility="CIDEr", scope="paragraph", weights="uniform", scores=None, lengths=None):
+    """The expected utility of every candidate, the pick of every group and the chosen rows, in one launch (svpc_consensus_pick; DESIGN
+    §11.7): ``pair`` (G, K, K, 6) float64 as ``consensus_pair_scores`` returns it for the same ``ids`` / ``plan`` / ``steps`` /
+    ``scope``; ``scores`` (T, K) float32 cumulative scores and ``lengths`` (T, K) int64 as the decode returns them (optional;
+    ``weights="posterior"`` needs ``scores``) → a dict: ``pick`` (G,) int32, ``expected`` (G, K) float64, ``ids`` (T, Lt) int64 the
+    chosen row of every sentence, ``row_pick`` (T,) int64 its index, ``scores`` (T,) float32 / ``lengths`` (T,) int64 or None."""
+    col = check_consensus(None, utility, scope, weights, scores)
+    T, K, lt, steps = _candidates("consensus_pick", ids, plan, steps)
+    table, G = plan.groups(steps, K, scope)
+    if pair.dtype != torch.float64 or tuple(pair.shape) != (G, K, K, CAPTION_SCORE_COLS) or not pair.is_contiguous() or pair.device != ids.device:
+        raise ValueError("consensus_pick: pair must be contiguous float64 (%d, %d, %d, %d) on the ids' device" % (G, K, K, CAPTION_SCORE_COLS))
+    for name, t, dt in (("scores", scores, torch.float32), ("lengths", lengths, torch.int64)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (T, K) or t.device != ids.device):
+            raise ValueError("consensus_pick: %s must be %s (%d, %d) on the ids' device" % (name, str(dt)[6:], T, K))
+    _need_gpu(ids)
+    ids = _c(ids)
+    scores = None if scores is None else _c(scores)
+    lengths = None if lengths is None else _c(lengths)
+    dev = ids.device
+    pick = torch.empty(G, dtype=torch.int32, device=dev)
+    expected = torch.empty(G, K, dtype=torch.float64, device=dev)
+    out_ids = torch.empty(T, lt, dtype=torch.int64, device=dev)
+    row_pick = torch.empty(T, dtype=torch.int64, device=dev)
+    out_scores = None if scores is None else torch.empty(T, dtype=torch.float32, device=dev)
+    out_len = None if lengths is None else torch.empty(T, dtype=torch.int64, device=dev)
+    _lib.call("consensus_pick", _p(pair), G, K, col, 1 if weights == "posterior" else 0, _p(scores), table.data_ptr() + 16 * G * K, T,
+              _p(ids), 1 if ids.dtype == torch.int64 else 0, lt, _p(lengths), _p(pick), _p(expected), _p(out_ids), _p(row_pick),
+              _p(out_scores), _p(out_len), _stream())
+    return dict(pick=pick, expected=expected, ids=out_ids, row_pick=row_pick, scores=out_scores, lengths=out_len)

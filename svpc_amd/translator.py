@@ -108,6 +108,12 @@ row=0)`` tells which of a recipe's ingredients each caption mentions (the rule o
 ``svpc_amd.metrics.IngredientF1`` accumulates its recall / precision / F1 — DESIGN §11.5).  ``Translator.caption_scores(dec_seq_list,
 plan, row=0)`` gives every video's Bleu_1…4, ROUGE_L and CIDEr against its reference paragraphs on the device
 (``svpc_amd.metrics.CaptionScores`` accumulates the epoch's — DESIGN §11.6).  ``translate_batch*`` themselves do not change.
+
+**Consensus selection** (minimum Bayes risk): ``Translator.consensus(dec_seq_list, plan, …)`` chooses one of the K rows
+of an n-best or sampling result without references — every candidate is scored against the others as pseudo-references (one of the six
+scores above, CIDEr by default, its idf from the plan's corpus) and the one with the highest expected utility wins, per video
+(``scope="paragraph"``: the same row k for all its sentences) or per sentence; ``translate_batch_consensus(model_inputs, plan,
+source="sample" | "nbest", num_candidates=K)`` is the decode followed by it.  On the device, without host synchronisation.
 """
 from __future__ import annotations
 
@@ -395,6 +401,51 @@ class Translator(object):
         words, ln, steps = self._clean(dec_seq_list, row)
         tokens, tok_len = ops.caption_tokens(words, ln, plan, steps)
         return ops.caption_score_counts(tokens, tok_len, plan)[1]
+
+    def consensus(self, dec_seq_list, plan, scores=None, lengths=None, utility="CIDEr", scope="paragraph", weights="uniform"):
+        """Consensus (minimum Bayes risk) selection among the K rows of a decode (``ops.consensus_pair_scores``, ``ops.consensus_pick``;
+        DESIGN §11.7): ``dec_seq_list`` per video (S_b, K, Lt) as ``translate_batch_sample`` / ``translate_batch_nbest`` return it,
+        ``plan`` = ``ReferenceCorpus.plan(videos, references=False)`` (or a plan with references) of the same videos, ``scores`` /
+        ``lengths`` the decode's score_list / length_list (optional; ``weights="posterior"`` weighs pseudo-reference j by
+        exp(c_j − max c) of its cumulative score and needs ``scores``).  ``scope="paragraph"``: candidate k is row k of all of a
+        video's sentences, one pick per video; ``"sentence"``: one pick per sentence.  → a namespace: ``dec_seq_list`` (per video
+        (S_b, Lt) int64, consecutive views of one buffer), ``pick_list`` (per video (S_b,) int64), ``expected_list`` (per video
+        (S_b, K) float64: the expected utility of the sentence's group), ``score_list`` / ``length_list`` (the chosen entries, or
+        None), and the device tensors behind them: ``pair_scores`` (G, K, K, 6) float64, ``pick`` (G,) int32.  Five launches, no host synchronisation, nothing uploaded for a recurring structure."""
+        ops.check_consensus(None, utility, scope, weights, scores)
+        ids, steps = ops.stack_captions(dec_seq_list)
+        if ids.dim() != 3:
+            raise ValueError("consensus: per-video ids must be (S_b, K, Lt), got %s" % (tuple(dec_seq_list[0].shape),))
+        sc = None if scores is None else ops.stack_captions(scores)[0]
+        ln = None if lengths is None else ops.stack_captions(lengths)[0]
+        pair, _ = ops.consensus_pair_scores(ids, plan, steps, PAD, EOS, IGNORE, scope=scope)
+        r = ops.consensus_pick(pair, ids, plan, steps, utility, scope, weights, sc, ln)
+        expected = r["expected"]
+        if scope == "paragraph":                 # a video's expected utilities on every one of its rows (a broadcast view: no launch)
+            exp_list = [expected[b].unsqueeze(0).expand(s, -1) for b, s in enumerate(steps)]
+        else:
+            exp_list = self._per_video(expected, steps)
+        return SimpleNamespace(dec_seq_list=self._per_video(r["ids"], steps), pick_list=self._per_video(r["row_pick"], steps),
+                               expected_list=exp_list, pair_scores=pair, pick=r["pick"],
+                               score_list=None if sc is None else self._per_video(r["scores"], steps),
+                               length_list=None if ln is None else self._per_video(r["lengths"], steps))
+
+    @torch.no_grad()
+    def translate_batch_consensus(self, model_inputs, plan, source="sample", num_candidates=4, utility="CIDEr", scope="paragraph",
+                                  weights="uniform", **decode_kw):
+        """``translate_batch_sample(num_samples=num_candidates)`` (``source="sample"``) or ``translate_batch_nbest(n_best=
+        num_candidates)`` (``"nbest"``; ``beam_size`` defaults to ``num_candidates``) followed by ``consensus`` →
+        (dec_seq_list, oov_word_dict, pick_list): one (S_b, Lt) int64 caption matrix per video, as greedy returns."""
+        ops.check_consensus(num_candidates, utility, scope, weights)
+        if source == "sample":
+            dec, oov, sc, ln = self.translate_batch_sample(model_inputs, num_samples=num_candidates, **decode_kw)
+        elif source == "nbest":
+            beam = decode_kw.pop("beam_size", num_candidates)
+            dec, oov, sc, ln = self.translate_batch_nbest(model_inputs, beam, num_candidates, **decode_kw)
+        else:
+            raise ValueError("source must be \"sample\" or \"nbest\", got %r" % (source,))
+        r = self.consensus(dec, plan, sc, ln, utility, scope, weights)
+        return r.dec_seq_list, oov, r.pick_list
 
     # ------------------------------------------------------------------ host part: everything that depends on the batch STRUCTURE only
     def _prepare(self, model, decode, batch_step_num, ingr_sep_masks, ingr_id_dict, oov_word_dict, S_pad, N, L, dev):

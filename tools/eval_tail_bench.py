@@ -1,4 +1,5 @@
-"""The scaffold of the evaluation-tail benchmarks (bench_decode_metrics.py, bench_ingredient_f1.py, bench_caption_scores.py): the
+"""The scaffold of the evaluation-tail benchmarks (bench_decode_metrics.py, bench_ingredient_f1.py, bench_caption_scores.py,
+bench_consensus.py): the
 BASELINE config 5 translator and batch (64 videos × 12 clips, vivt, D = 768, L = 6; bf16x3, hipGraph-replayed greedy decode) on the
 device, timed legs that alternate, and a leg's statistics."""
 import argparse
@@ -54,6 +55,7 @@ def config5(a):
 
         def decode():
             return tr.translate_batch(syn.translate_inputs(b))[0]
+        decode.translator = tr                     # (bench_consensus.py decodes K samples with the same translator)
         yield cfg, dev, b, decode
 
 
