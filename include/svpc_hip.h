@@ -629,6 +629,32 @@ int svpc_consensus_pair_scores(const unsigned short* tokens, const int* tok_len,
 int svpc_consensus_pick(const double* pair, int n_grp, int k, int col, int posterior, const float* scores, const int* grp_off,
                         long long n_rows, const void* ids, int ids64, int lt, const long long* lengths, int* pick, double* expected,
                         long long* out_ids, long long* row_pick, float* out_scores, long long* out_len, svpc_stream_t stream);
+
+/* ---- forced decoding: the decoder's scores of GIVEN captions (the GOLD score / gold perplexity of the reference decoder's
+ *      OpenNMT lineage).  n_cap caption rows of lt positions, extended ids, position 0 BOS; the decoder side runs once over all positions,
+ *      score row r·lt + i scores position p = i + 1 of caption r.  A caption ends finished at its first eos (len = p) or unfinished before
+ *      its first pad / ignore (len = p − 1), else len = lt − 1. */
+/* ids (n_cap, lt) int64 (ids_i64) or int32 -> model_ids (an id outside [0, vocab) is unk; pad after position len), mask (fp32, 1 on
+ * positions 0 … len), tgt (the id of every position as a score column; −2 when it fits no int32), len, finished (n_cap,) */
+int svpc_force_inputs(const void* ids, int ids_i64, int n_cap, int lt, int vocab, int unk, int eos, int pad, int ignore, int* model_ids,
+                      float* mask, int* tgt, int* len, int* finished, svpc_stream_t stream);
+/* one wave per score row (r, i), i < len[r]: scores (>= n_cap·lt rows of ld floats; row_c[r] <= max_c <= ld columns) — probabilities, or
+ * logits when logits != 0.  Candidates: columns c < row_c[r], c != unk, in order of higher raw value then lower column.  Out, at
+ * r·(lt − 1) + i: step = the step score of column w = tgt[r·lt + i + 1] as svpc_beam_step's (fp64, rounded once: log p, −inf for p <= 0; or
+ * logit − the log-sum-exp of the row without unk), rank = the candidates ahead of w, top / top_step = the first candidate and its step
+ * score.  w no candidate (unk, < 0, >= row_c[r]): rank −1, step −inf, or 0 when skip != 0.  Entries with i >= len[r] are not written. */
+int svpc_force_score(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, int n_cap, int lt, int logits,
+                     int unk, int skip, float* step, int* rank, int* top, float* top_step, svpc_stream_t stream);
+/* per caption row: cum = fp32(cum + step) over i < len[r] in order, n_scored = the positions that contributed (all of them; with skip != 0
+ * those whose target is a candidate); the entries i >= len[r] of step / rank / top / top_step become 0 / −1 / −1 / 0 */
+int svpc_force_finish(const int* tgt, const int* len, const int* row_c, int n_cap, int lt, int unk, int skip, float* step, int* rank,
+                      int* top, float* top_step, float* cum, int* n_scored, svpc_stream_t stream);
+/* acc (9,) float64 += captions, positions scored, sum of cum and of n_scored over the captions with a finite cum, captions with a
+ * non-finite cum, positions of rank 0, sum of rank and count of the ranked positions (rank >= 0, i < len[r]), finished captions — one
+ * workgroup, fixed summation order */
+int svpc_force_accum(const float* cum, const int* n_scored, const int* finished, const int* len, const int* rank, int n_cap, int lt,
+                     double* acc, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

@@ -26,6 +26,7 @@
 // positions that are all words, so none spans two sentences.  Each live row's bans (its own and the history's) are merged into an LDS
 // bitmap of kBanCols bits, read only by a column that would enter a lane's top-B.
 #include "common.h"
+#include "score_row.h"
 
 #include <climits>
 
@@ -35,8 +36,6 @@ constexpr int kBeamMax = 8;
 constexpr int kBeamThreads = 256;
 constexpr int kBanCols = 4096;                     // paragraph scope: columns of a row's ban bitmap (ops.SAMPLE_COLS_MAX)
 constexpr int kBanWords = kBanCols / 32;
-
-__device__ __forceinline__ bool raw_better(float v, int c, float w, int d) { return v > w || (v == w && c < d); }
 
 // insert (v, c) into the sorted top-B list (val, idx); entries past the last real one hold (-inf, INT_MAX)
 template <int B>
@@ -49,15 +48,6 @@ __device__ __forceinline__ void topb_insert(float (&val)[B], int (&idx)[B], floa
             val[k] = v; idx[k] = c; v = tv; c = ti;
         }
     }
-}
-
-__device__ __forceinline__ double wave_max_d(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 struct BeamArgs {
@@ -185,17 +175,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
             continue;
         }
         const float* row = a.scores + (size_t)r * a.ld;
-        double lse = 0.0;
-        if (a.logits) {                           // log-sum-exp over the row's columns, UNK excluded (fp64)
-            float m = -INFINITY;
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk) m = fmaxf(m, row[c]);
-            const double md = wave_max_d((double)m);
-            double sm = 0.0;
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk) sm += exp((double)row[c] - md);
-            lse = md + log(wave_sum_d(sm));
-        }
+        const double lse = a.logits ? row_lse(row, C, a.unk, lane) : 0.0;     // log-sum-exp over the row's columns, UNK excluded (fp64)
         float val[B]; int idx[B];
 #pragma unroll
         for (int k = 0; k < B; ++k) { val[k] = -INFINITY; idx[k] = INT_MAX; }
@@ -223,9 +203,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
 #pragma unroll
             for (int k = 1; k < B; ++k) if (lane == k) { v = val[k]; c = idx[k]; }
             if (c != INT_MAX) {
-                float step;
-                if (a.logits) step = (float)((double)v - lse);
-                else step = v > 0.f ? (float)log((double)v) : -INFINITY;
+                const float step = step_score(v, a.logits, lse);
                 const int e = h * B + lane;
                 const float cu = p_cum[h] + step;
                 c_key[e] = a.lp ? (double)cu / a.lp[pl] : (double)cu;

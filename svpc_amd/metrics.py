@@ -10,7 +10,8 @@ updated by two small kernels per video; ``result()`` is the only host read-back.
 evaluateCaptionsDiversity.py:219-282, get_caption_stat.py) from the translator's id matrices, three launches per batch and no host
 synchronisation until ``result()``.  ``IngredientF1`` adds the ingredient-prediction recall / precision / F1 of
 src/calculate_ingredient_f1.py from the same clean captions, ``CaptionScores`` Bleu_1…4, ROUGE_L and CIDEr against
-reference paragraphs (densevid_eval/para-evaluate.py without METEOR).
+reference paragraphs (densevid_eval/para-evaluate.py without METEOR), ``ForcedScores`` the gold score and perplexity of
+given captions under decoding conditions (the GOLD numbers of the reference decoder's OpenNMT lineage).
 """
 from __future__ import annotations
 
@@ -265,3 +266,37 @@ class CaptionScores:
         res.update(ROUGE_L=rouge / nv if nv else 0.0, CIDEr=cider / nv if nv else 0.0, num_videos=nv, testlen=v[8], reflen=reflen,
                    correct=v[0:4], guess=v[4:8])
         return res
+
+
+class ForcedScores:
+    """Running gold score / perplexity of an evaluation epoch from ``Translator.score_captions`` results, kept on the
+    device: ``update(scored)`` takes the namespace it returns (one launch, fixed summation order, nothing uploaded — capturable);
+    ``compute()`` is the only read-back.
+
+    accumulator (9,) float64: captions, positions scored (Σ n_scored), Σ cum and Σ n_scored over the captions with a finite cum, captions
+    with a non-finite cum, positions of rank 0, Σ rank and the count of the ranked positions, finished captions."""
+
+    def __init__(self, device="cuda"):
+        self.device = _gpu_device(device)
+        self.acc = torch.zeros(ops.FORCE_ACC_COLS, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        self.acc.zero_()
+
+    def update(self, scored):
+        ops.force_accum(scored.cum, scored.n_scored, scored.finished, scored.length, scored.rank, self.acc)
+        return self.acc
+
+    def compute(self):
+        """→ captions, tokens (positions scored), score_sum (Σ cum over the finite captions), ppl = exp(−score_sum / their positions),
+        inf_share (captions with cum = −inf), top1 (share of ranked positions where the target is the decoder's first candidate),
+        mean_rank (over the ranked positions), finished_share.  A ratio without a denominator is 0 (ppl: nan)."""
+        import math
+        v = [float(x) for x in self.acc.cpu()]
+        n, ranked = v[0], v[7]
+        return dict(captions=int(n), tokens=int(v[1]), score_sum=v[2],
+                    ppl=math.exp(-v[2] / v[3]) if v[3] else float("nan"), inf_share=v[4] / n if n else 0.0,
+                    top1=v[5] / ranked if ranked else 0.0, mean_rank=v[6] / ranked if ranked else 0.0,
+                    finished_share=v[8] / n if n else 0.0)
+
+    result = compute

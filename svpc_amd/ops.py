@@ -3164,3 +3164,129 @@ def consensus_pick(pair, ids, plan, steps, utility="CIDEr", scope="paragraph", w
               _p(ids), 1 if ids.dtype == torch.int64 else 0, lt, _p(lengths), _p(pick), _p(expected), _p(out_ids), _p(row_pick),
               _p(out_scores), _p(out_len), _stream())
     return dict(pick=pick, expected=expected, ids=out_ids, row_pick=row_pick, scores=out_scores, lengths=out_len)
+
+
+FORCE_MAX = 16                  # given captions per sentence (what ``consensus`` takes)
+FORCE_UNK = ("bar", "skip")
+
+
+def check_force(ids, lt=None, steps=None, unk="bar"):
+    """Host checks of forced scoring: ``ids`` the stacked given captions, (T, K, Lt) or (T, Lt) int32 / int64 extended ids
+    with 1 ≤ K ≤ 16; ``lt`` the model's Lt when the caller has one; ``steps`` the videos' sentence counts, which must add up to T;
+    ``unk`` "bar" or "skip".  ValueError for each; ``SvpcKernelError`` for ids that are not on the GPU (no CPU fallback exists).
+    → (T, K, Lt, skip flag)."""
+    if unk not in FORCE_UNK:
+        raise ValueError("unk must be one of %s, got %r" % (", ".join(FORCE_UNK), unk))
+    if not torch.is_tensor(ids) or ids.dim() not in (2, 3) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError("forced scoring takes int32 / int64 ids of shape (T, K, Lt) or (T, Lt), got %s"
+                         % ((tuple(ids.shape), ids.dtype) if torch.is_tensor(ids) else type(ids).__name__,))
+    T, K, n = (ids.shape[0], 1, ids.shape[1]) if ids.dim() == 2 else tuple(ids.shape)
+    if not 1 <= K <= FORCE_MAX:
+        raise ValueError("forced scoring takes 1..%d captions per sentence, got K = %d" % (FORCE_MAX, K))
+    if n < 2:
+        raise ValueError("captions need at least two positions (BOS and one word), got Lt = %d" % n)
+    if lt is not None and n != int(lt):
+        raise ValueError("captions of %d positions, the model's Lt is %d" % (n, lt))
+    if steps is not None and (any(int(s) < 0 for s in steps) or sum(int(s) for s in steps) != T):
+        raise ValueError("the videos' sentence counts %r do not add up to the %d caption rows given" % (list(steps), T))
+    if not ids.is_cuda:
+        raise _lib.SvpcKernelError("svpc_amd.ops: forced scoring runs on the GPU only (no CPU fallback exists)")
+    return T, K, n, 1 if unk == "skip" else 0
+
+
+def force_inputs(ids, vocab, unk_id, eos, pad, ignore=-1):
+    """What the decoder and ``force_score`` need of given captions (svpc_force_inputs): ``ids`` (T, K, Lt) or (T, Lt) int32 / int64
+    extended ids → (model_ids (R, Lt) int32 — an id outside the text vocabulary is ``unk_id``, ``pad`` after the caption's end —,
+    mask (R, Lt) fp32 — 1 on positions 0 … len —, tgt (R, Lt) int32 target columns, len (R,) int32, finished (R,) int32), R = T·K."""
+    if not 0 <= int(unk_id) < int(vocab):
+        raise ValueError("force_inputs: the UNK id must lie inside the text vocabulary")
+    T, K, lt, _ = check_force(ids)
+    _need_gpu(ids)
+    ids = _c(ids)
+    R, dev = T * K, ids.device
+    model_ids = torch.empty(R, lt, dtype=torch.int32, device=dev)
+    mask = torch.empty(R, lt, dtype=torch.float32, device=dev)
+    tgt = torch.empty(R, lt, dtype=torch.int32, device=dev)
+    ln = torch.empty(R, dtype=torch.int32, device=dev)
+    fin = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("force_inputs", _p(ids), 1 if ids.dtype == torch.int64 else 0, R, lt, int(vocab), int(unk_id), int(eos), int(pad), int(ignore),
+              _p(model_ids), _p(mask), _p(tgt), _p(ln), _p(fin), _stream())
+    return model_ids, mask, tgt, ln, fin
+
+
+def force_score(scores, row_c, tgt, length, logits, unk_id, unk="bar", max_cols=None):
+    """The scores of given captions from the decoder's score matrix (svpc_force_score, svpc_force_finish: two launches):
+    ``scores`` (≥ R·Lt, ≥ C) fp32 — row r·Lt + i is step i of caption row r; probabilities, or logits when ``logits`` —, ``row_c`` the R
+    rows' column counts C_r (an Idx or host ints), ``tgt`` (R, Lt) / ``length`` (R,) int32 as ``force_inputs`` returns them,
+    ``max_cols`` max(row_c) when the caller knows it → a dict: ``cum`` (R,) fp32, ``n_scored`` (R,) int32, and (R, Lt − 1) ``step`` fp32,
+    ``rank`` int32, ``top`` int32, ``top_step`` fp32.  Reads the score matrix once (twice in logits mode); allocates the six results."""
+    if unk not in FORCE_UNK:
+        raise ValueError("unk must be one of %s, got %r" % (", ".join(FORCE_UNK), unk))
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("force_score: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("force_score: scores must be fp32 (>= R·Lt, C) rows with unit column stride")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("force_score: length must be contiguous int32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("force_score: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and min(rc.host) < 1):
+        raise ValueError("force_score: rows of 1..%d columns, inside the score matrix" % scores.shape[1])
+    _need_gpu(scores)
+    dev = scores.device
+    skip = 1 if unk == "skip" else 0
+    step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+    top_step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+    rank = torch.empty(R, lt - 1, dtype=torch.int32, device=dev)
+    top = torch.empty(R, lt - 1, dtype=torch.int32, device=dev)
+    cum = torch.empty(R, dtype=torch.float32, device=dev)
+    n_scored = torch.empty(R, dtype=torch.int32, device=dev)
+    rcd = rc.dev(dev)
+    _lib.call("force_score", _p(scores), scores.stride(0), _p(rcd), max_c, _p(tgt), _p(length), R, lt, 1 if logits else 0, int(unk_id), skip,
+              _p(step), _p(rank), _p(top), _p(top_step), _stream())
+    _lib.call("force_finish", _p(tgt), _p(length), _p(rcd), R, lt, int(unk_id), skip, _p(step), _p(rank), _p(top), _p(top_step), _p(cum),
+              _p(n_scored), _stream())
+    return dict(cum=cum, n_scored=n_scored, step=step, rank=rank, top=top, top_step=top_step)
+
+
+def ptr_attn_gate_groups(dec, proj, bank, step_ne, lt, group_rows, w, b):
+    """Pointer attention and generation gate (``ptr_attn_gate``, inference) for ``len(group_rows)`` sentences' worth of rows per step row
+    of the bank: ``dec`` (T·G·lt, D) holds G groups of ``lt`` rows per sentence, ``group_rows[g]`` = (row_off, row_len) int32 device
+    tables naming group g's rows of every sentence.  One launch per group into shared results, so the bank and its projection are not
+    replicated → (pi (T·G·lt, e_max), p_gen (T·G·lt, 1)).  ``SvpcKernelError`` for a shape the kernel does not take."""
+    T, e_max, D = bank.shape
+    G = len(group_rows)
+    if (not dec.is_cuda or dec.dtype != torch.float32 or D % 4 or tuple(w.shape) != (1, 2 * D) or b is None or b.numel() != 1 or lt > 32
+            or e_max > 32 or tuple(dec.shape) != (T * G * lt, D) or w.dtype != torch.float32 or (w.data_ptr() % 16) or lo_off(dec) is not None):
+        raise _lib.SvpcKernelError("ptr_attn_gate_groups: fp32 rows of D %% 4 == 0 columns, at most 32 positions and 32 entities per sentence")
+    _need_gpu(dec)
+    dec, proj, bank, w = _c(dec), _c(proj), _c(bank), _c(w)
+    dev = dec.device
+    ne = as_idx(step_ne).dev(dev)
+    pi = torch.empty(dec.shape[0], e_max, dtype=torch.float32, device=dev)
+    g = torch.empty(dec.shape[0], 1, dtype=torch.float32, device=dev)
+    for ro, rl in group_rows:
+        _lib.call("ptr_attn_gate_fwd_r", _p(dec), _p(proj), _p(bank), _p(ne), _p(pi), _p(w), _p(b), _p(g), T, lt, e_max, D, _p(ro), _p(rl),
+                  _stream())
+    return pi, g
+
+
+FORCE_ACC_COLS = 9              # captions, positions, Σ cum / Σ n_scored (finite captions), −inf captions, rank-0, Σ rank, ranked, finished
+
+
+def force_accum(cum, n_scored, finished, length, rank, acc):
+    """acc (9,) float64 += the sums ``metrics.ForcedScores`` keeps (svpc_force_accum, fixed order): ``cum`` fp32, ``n_scored`` /
+    ``finished`` / ``length`` int32 of R caption rows (any shape of R elements) and ``rank`` (R, Lt − 1) int32, as ``force_score`` /
+    ``Translator.score_captions`` return them."""
+    R = cum.numel()
+    if cum.dtype != torch.float32 or rank.dtype != torch.int32 or rank.dim() < 2 or rank.numel() != R * rank.shape[-1] or any(
+            t.dtype != torch.int32 or t.numel() != R or t.device != cum.device for t in (n_scored, finished, length)) or rank.device != cum.device:
+        raise ValueError("force_accum: cum fp32, n_scored / finished / length int32 of R rows and rank int32 (R, Lt - 1), on one device")
+    _accumulator("force_accum", "acc", acc, torch.float64, FORCE_ACC_COLS, cum, "scores")
+    _need_gpu(cum)
+    cum, n_scored, finished, length, rank = (_c(t) for t in (cum, n_scored, finished, length, rank))
+    _lib.call("force_accum", _p(cum), _p(n_scored), _p(finished), _p(length), _p(rank), R, rank.shape[-1] + 1, _p(acc), _stream())
+    return acc

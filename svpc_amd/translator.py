@@ -114,6 +114,29 @@ of an n-best or sampling result without references — every candidate is scored
 scores above, CIDEr by default, its idf from the plan's corpus) and the one with the highest expected utility wins, per video
 (``scope="paragraph"``: the same row k for all its sentences) or per sentence; ``translate_batch_consensus(model_inputs, plan,
 source="sample" | "nbest", num_candidates=K)`` is the decode followed by it.  On the device, without host synchronisation.
+
+**Forced scoring** (the GOLD score / gold perplexity of the reference decoder's OpenNMT lineage):
+``Translator.score_captions(model_inputs, dec_seq_list, unk="bar")`` scores GIVEN captions under decoding conditions (text half masked,
+``log p`` of the mixed pointer-generator distribution).  The definition, restated by tests/forced_score_reference.py:
+
+- captions come in the shape every ``translate_batch*`` returns: per video (S_b, Lt) or (S_b, K, Lt), int64 or int32 extended ids,
+  1 ≤ K ≤ 16, y_0 = BOS; row r = t·K + k has C_r = V + X columns of its video (X = 0 in ``video`` mode);
+- step i = 0 … Lt − 2 scores position p = i + 1 with target w = y_p while the row is live: w == EOS: its step score is added, the row is
+  finished, len = p; w == PAD or w == IGNORE: the row ends unfinished, len = p − 1, nothing is added and nothing after it is looked at;
+  otherwise the step score of column w is added; a row that never ends has len = Lt − 1;
+- the step score is exactly the decoder's (fp64, rounded once to fp32: ``log p``, −inf for p ≤ 0; ``video`` mode the logit minus the
+  log-sum-exp of the row's columns without UNK); a target that is no candidate of the decoder (w == UNK, w < 0, w ≥ C_r) follows ``unk``:
+  ``"bar"`` (default) −inf, ``"skip"`` contributes 0 and is not counted in ``n_scored``;
+- cum = fp32(cum + s) in position order, the decoder's own accumulation; the model-side input at position p is w if 0 ≤ w < V, else UNK;
+- per row: ``cum`` (T, K) fp32, ``len`` / ``n_scored`` / ``finished`` (T, K) int32; per position (T, K, Lt − 1): ``step`` fp32 (0 past the
+  end), ``rank`` int32 — the candidate columns (c < C_r, c ≠ UNK) that precede w in the decoder's order (higher raw value, then lower
+  column; 0 is greedy's pick; −1 past the end or for a non-candidate) —, ``top`` int32 the best candidate column and ``top_step`` fp32 its
+  step score (−1 and 0 past the end);
+- the decoder side runs ONCE over the T·K caption rows of Lt positions (causal ∧ pad mask), not Lt − 1 times; the K captions of a
+  sentence share its memory rows and pointer bank; ``incremental`` makes no difference, ``two_streams`` is ignored.
+
+``Translator.gold_captions(input_labels_list, batch_step_num)`` builds the references of a batch as a ``dec_seq_list`` on the device;
+``svpc_amd.metrics.ForcedScores`` accumulates gold score, perplexity, top-1 agreement and mean rank.
 """
 from __future__ import annotations
 
@@ -123,7 +146,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .model import BatchPlan, _Ctx
+from .model import BatchPlan, StateAwareRecursiveTransformer, _Ctx
 from .ops import check_beam_controls, check_sampling, exclusion_bitmap, length_penalty_table     # (host-side: bound here, not through ``ops``)
 from .ops_common import ACT_RELU, BulkUpload, Idx, SeqInfo
 from .synthetic import BOS, EOS, IGNORE, PAD, UNK
@@ -140,7 +163,7 @@ def ids_to_sentences(clean, lens, idx2word, oov_word_dict):
     return [" ".join(idx2word[w] if w in idx2word else oov[w] for w in row[:int(n)]) for row, n in zip(rows, ns)]
 
 
-GREEDY, BEAM, SAMPLE = "greedy", "beam", "sample"
+GREEDY, BEAM, SAMPLE, FORCE = "greedy", "beam", "sample", "force"
 
 
 class Decode(object):
@@ -148,12 +171,13 @@ class Decode(object):
     ``kind``: GREEDY, BEAM or SAMPLE; ``width``: the rows per sentence (beam width B, samples R; greedy 1); ``controls`` / ``ctl_key``: the
     checked decoding controls and their key (None: all off); ``sampling``: the checked (τ, k, q, m).  ``key`` is the decode's part of the
     plan cache key.  Outside it: ``n_best`` — the rows per sentence the call returns (0: the chosen caption alone; it only slices the
-    result) — and ``seed``, this call's seed (a captured input)."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed")
+    result) — and ``seed``, this call's seed (a captured input).  FORCE (``score_captions``): ``width`` is the K given captions per
+    sentence, ``sampling`` holds (unk rule, id dtype) — part of the key — and ``given`` this call's (T, K, Lt) ids (a captured input)."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given")
 
-    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None):
-        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed = (
-            kind, width, controls, ctl_key, n_best, sampling, seed)
+    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None):
+        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given = (
+            kind, width, controls, ctl_key, n_best, sampling, seed, given)
 
     @property
     def ranked(self):
@@ -175,6 +199,7 @@ class DecodePlan(object):
                  "controls",                                    # ranked: ops.beam_step's keywords (device tables)
                  "rounds", "rows_max",                          # paragraph scope: the round tables, the largest round's rows
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
+                 "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
                  "graphs")                                      # replay stream → (graph, captured inputs, outputs, signature)
 
@@ -431,6 +456,50 @@ class Translator(object):
                                length_list=None if ln is None else self._per_video(r["lengths"], steps))
 
     @torch.no_grad()
+    def score_captions(self, model_inputs, dec_seq_list, unk="bar"):
+        """Forced decoding: what the model thinks of GIVEN captions (module docstring, **Forced scoring**).
+        ``model_inputs`` as ``translate_batch`` takes them (the text half of its ids / masks is blanked in place, as there);
+        ``dec_seq_list`` per video (S_b, Lt) or (S_b, K, Lt) int64 / int32 extended ids, 1 ≤ K ≤ 16, position 0 BOS — what any
+        ``translate_batch*`` returns, or ``gold_captions``; ``unk`` "bar" or "skip".  → a namespace of per-video lists (consecutive views
+        of one buffer each): ``score_list`` (S_b, K) fp32 cum, ``length_list`` / ``finished_list`` / ``n_scored_list`` (S_b, K) int32,
+        ``step_list`` / ``top_step_list`` (S_b, K, Lt − 1) fp32, ``rank_list`` / ``top_list`` (S_b, K, Lt − 1) int32 — K = 1 for 2-D
+        input — and the flat (T, …) device tensors behind them: ``cum``, ``length``, ``finished``, ``n_scored``, ``step``, ``rank``,
+        ``top``, ``top_step``.  One decoder pass over T·K·Lt rows, no host synchronisation; replayed as one graph with ``graph=True``.
+        Device memory: the (T·K·Lt, V) logits and, in pointer modes, the (T·K·Lt, V + X) probabilities in fp32 (2 · 257 MB at 64
+        videos × 12 clips, K = 4, Lt = 22, V ≈ 950) plus the decoder's activations of T·K·Lt rows; no chunking over sentences.
+        ValueError on the host for K, the ids' shape / dtype / Lt, a mismatch with ``batch_step_num`` and an unknown ``unk``;
+        ``SvpcKernelError`` for ids or inputs that are not on the GPU; ``two_streams`` is ignored."""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        if steps != [int(s) for s in model_inputs[11]]:
+            raise ValueError("score_captions: the captions' rows per video %r are not the batch's step counts %r" % (steps, list(model_inputs[11])))
+        T, K, _, _ = ops.check_force(ids, self.max_t_len, steps, unk)
+        r = self._translate(model_inputs, self.model, decode=Decode(FORCE, K, sampling=(unk, ids.dtype), given=ids))
+        lists = {name: self._per_video(r[k], steps) for name, k in (
+            ("score_list", "cum"), ("length_list", "length"), ("finished_list", "finished"), ("n_scored_list", "n_scored"),
+            ("step_list", "step"), ("rank_list", "rank"), ("top_list", "top"), ("top_step_list", "top_step"))}
+        return SimpleNamespace(**lists, **r)
+
+    def gold_captions(self, input_labels_list, batch_step_num):
+        """The reference captions of a batch as a ``dec_seq_list`` for ``score_captions``, on the device: ``input_labels_list`` the
+        per-step (N, Lv + Lt) label tensors of the training batch (the label at text position j is the word at caption position
+        j + 1; IGNORE elsewhere) → per video (S_b, Lt) int64: BOS, then the labels of text positions 0 … Lt − 2 with IGNORE turned into
+        PAD — consecutive views of one buffer.  One index upload per call, no read-back."""
+        Lv, Lt = self.max_v_len, self.max_t_len
+        lab = input_labels_list                                # (S, N, L): the per-step tensors stacked (zero-copy for a stacked loader)
+        if isinstance(lab, (list, tuple)):
+            lab = StateAwareRecursiveTransformer._stacked(list(lab))
+        steps = [int(s) for s in batch_step_num]
+        if lab.dim() != 3 or lab.shape[2] < Lv + Lt or len(steps) != lab.shape[1] or any(not 0 <= s <= lab.shape[0] for s in steps):
+            raise ValueError("gold_captions: labels must be (S, N, >= Lv + Lt) with one step count <= S per video")
+        N = lab.shape[1]
+        rows = torch.tensor([s * N + b for b, n in enumerate(steps) for s in range(n)], dtype=torch.int64).to(lab.device)
+        text = lab.reshape(-1, lab.shape[2])[:, Lv:Lv + Lt - 1].index_select(0, rows).to(torch.int64)
+        out = torch.empty(len(rows), Lt, dtype=torch.int64, device=lab.device)
+        out[:, 0] = BOS
+        out[:, 1:] = torch.where(text == IGNORE, torch.full_like(text, PAD), text)
+        return self._per_video(out, steps)
+
+    @torch.no_grad()
     def translate_batch_consensus(self, model_inputs, plan, source="sample", num_candidates=4, utility="CIDEr", scope="paragraph",
                                   weights="uniform", **decode_kw):
         """``translate_batch_sample(num_samples=num_candidates)`` (``source="sample"``) or ``translate_batch_nbest(n_best=
@@ -465,7 +534,9 @@ class Translator(object):
         T, W = plan.T, decode.width
         c_list = [V + x_ for x_ in n_oov]
         dp = DecodePlan(key=key, spans=spans, plan=plan, c_list=c_list, T=T, kind=decode.kind, width=W, ranked=decode.ranked)
-        if not self.incremental:
+        if decode.kind == FORCE:
+            self._prepare_force(model, dp, decode, dicts, c_list, dev)
+        elif not self.incremental:
             dp.ptr_all, dp.x_all = model._ptr_plan(dicts, c_list, Lt, plan.step_ne, plan.row_vid), Idx([n_oov[b] for b in plan.row_vid.host])
         else:
             # hypothesis rows t·W + h: the pointer plan of W rows per sentence (ptr_attn_gate / ptr_mix_loss with lt = W)
@@ -495,6 +566,26 @@ class Translator(object):
             self._preps.clear()
         self._preps[key] = dp
         return dp
+
+    @staticmethod
+    def _prepare_force(model, dp, decode, dicts, c_list, dev):
+        """Forced scoring's part of the plan: the T·K caption rows of Lt positions as one decoder pass.  The K captions of a sentence
+        share its memory rows through the cross segmentation (row r over the memory rows of sentence r // K) and its pointer bank
+        through one (row offset, row count) table per k; the pointer plan has K·Lt rows per sentence; the given ids have a buffer of
+        their own, which a captured graph reads."""
+        plan, T, K, Lt = dp.plan, dp.T, dp.width, model.config.max_t_len
+        n_mem, R = model._n_mem(), dp.T * dp.width
+        dp.unk, id_dtype = decode.sampling
+        dp.given = torch.empty(T, K, Lt, dtype=id_dtype, device=dev)
+        dp.cap_c = Idx([c_list[b] for b in plan.step_vid.host for _ in range(K)])
+        dp.ptr_force = model._ptr_plan(dicts, c_list, K * Lt, plan.step_ne, Idx([b for b in plan.step_vid.host for _ in range(K * Lt)]))
+        if K == 1:
+            dp.force_self, dp.force_cross = plan.seq_dec_self, plan.seq_dec_cross
+        else:
+            dp.force_self = SeqInfo.uniform(R, Lt, Lt, dev)
+            dp.force_cross = SeqInfo([r * Lt for r in range(R)], [Lt] * R, [(r // K) * n_mem for r in range(R)], [n_mem] * R, dev)
+        lens = torch.full((T,), Lt, dtype=torch.int32, device=dev)
+        dp.group_rows = [(torch.tensor([(t * K + k) * Lt for t in range(T)], dtype=torch.int32, device=dev), lens) for k in range(K)]
 
     @staticmethod
     def _paragraph_rounds(model, plan, dicts, c_list, n_oov, B, Lt, dev):
@@ -585,7 +676,9 @@ class Translator(object):
             bank = None
 
         stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
-        if not self.incremental:
+        if dp.kind == FORCE:
+            out = self._force_pass(model, dp, mem, bank, cx)
+        elif not self.incremental:
             out = self._greedy_rerun(model, dp, mem, bank, cx)
         else:
             side = _DecoderSide(model, cx, mem, bank, self._text_table(model, Lt, cx, dev), T)
@@ -634,6 +727,33 @@ class Translator(object):
                 scores, _ = model._lm_probs(dec, bank, dp.ptr_all, cx)
             nxt_ext, nxt = ops.greedy_pick(scores, dp.ptr_all["row_c"], dp.x_all, Lt, i, UNK)
         return (text if mode == "video" else ext).unsqueeze(1), None, None
+
+    @staticmethod
+    def _force_pass(model, dp, mem, bank, cx):
+        """Forced scoring: ONE pass of the decoder side over the Lt positions of all T·K given captions (the all-positions form of
+        ``_greedy_rerun``: causal ∧ pad mask, so position i sees positions 0 … i of its own caption), then ``ops.force_score`` over the
+        (T·K·Lt, C) score matrix → a dict of flat device tensors (``score_captions``)."""
+        cfg = model.config
+        K, T, Lt, V = dp.width, dp.T, cfg.max_t_len, cfg.vocab_size
+        text, tmask, tgt, length, fin = ops.force_inputs(dp.given, V, UNK, EOS, PAD, IGNORE)
+        xt = model.text_embeddings.run(text.reshape(-1), Lt, cx)
+        dec = model.decoder.run(xt, tmask.reshape(-1), mem, dp.force_self, dp.force_cross, None, cx)
+        logits = model.decoder_classifier.run(dec, cx.eps)
+        if cfg.model_mode == "video":
+            scores = logits                                   # raw logits: the step score is their log_softmax (translator.py:159)
+        else:
+            pl = dp.ptr_force
+            pi = g = None
+            if bank is not None:        # the K captions of a sentence read its bank: one launch per k, nothing replicated
+                pi, g = ops.ptr_attn_gate_groups(dec, model.bank_projection(bank), bank, pl["step_ne"], Lt, dp.group_rows,
+                                                 model.pgen_linear[0].weight, model.pgen_linear[0].bias)
+            labels = torch.full((dec.shape[0],), -1, dtype=torch.int32, device=dec.device)
+            scores = ops.ptr_mix_loss(logits, g, pi, labels, pl["row_c"], pl["row_vid"], pl["csr_off"], pl["csr_ent"], pl["csr_id"],
+                                      pl["csr_w"], pl["c_max"], model.label_smoothing)[0]
+        r = ops.force_score(scores, dp.cap_c, tgt, length, cfg.model_mode == "video", UNK, dp.unk, max_cols=max(dp.c_list))
+        return dict(cum=r["cum"].view(T, K), length=length.view(T, K), finished=fin.view(T, K), n_scored=r["n_scored"].view(T, K),
+                    step=r["step"].view(T, K, Lt - 1), rank=r["rank"].view(T, K, Lt - 1), top=r["top"].view(T, K, Lt - 1),
+                    top_step=r["top_step"].view(T, K, Lt - 1))
 
     @staticmethod
     def _self_segs(dp, Lt, dev):
@@ -740,6 +860,8 @@ class Translator(object):
         dev = video_features_list[0].device
         if decode.kind == SAMPLE and dev.type != "cuda":
             raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
+        if decode.kind == FORCE and dev.type != "cuda":
+            raise ops._lib.SvpcKernelError("forced scoring runs on the GPU only (no CPU fallback exists)")
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
         # tensors are consecutive slices of one buffer (the usual collate output; model._stacked sees it) that is three launches on the
         # stacked views instead of three per step
@@ -766,6 +888,8 @@ class Translator(object):
                                list(oov_word_dict[lo:hi]), S_pad, n, L, dev)
             if dp.seed_src is not None:       # the seed source of this call: a captured input, like the batch tensors
                 dp.seed_src.copy_(torch.tensor([0, 0] if decode.seed is None else [1, decode.seed], dtype=torch.int64))
+            if dp.given is not None:          # the captions to score: a captured input too
+                dp.given.copy_(decode.given.view(dp.given.shape))
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
                 out = self._decode_core(model, dp, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
@@ -797,6 +921,8 @@ class Translator(object):
                     plans_outs.append(part(lo, hi, st))
             for st in (sa, sb):
                 cur.wait_stream(st)
+        if decode.kind == FORCE:            # (one part: the halves are greedy's) the flat result, ``score_captions`` splits it
+            return plans_outs[0][1]
         # every strategy's result: ids (T, K, Lt), cum (T, K) or None, len (T, K) or None.  The call returns the first n_best of the K rows
         # per sentence, or (n_best 0) the chosen caption alone, without lengths
         k = decode.n_best
@@ -866,4 +992,6 @@ class Translator(object):
         for dst, s_ in zip(static, src):
             dst.copy_(s_)
         graph.replay()
+        if isinstance(out, dict):
+            return {k: v.clone() for k, v in out.items()}
         return tuple(o.clone() if o is not None else None for o in out)
