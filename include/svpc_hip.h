@@ -520,6 +520,18 @@ int svpc_beam_step_para(const float* scores, int ld, const int* row_c, const int
                         int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
                         int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, const int* hist, const int* hist_desc,
                         int bos, svpc_stream_t stream);
+/* diverse (group) beam search (Vijayakumar et al. 2016, arXiv 1610.02424; Hamming diversity): svpc_beam_step_ctl over `beam` rows per
+ * sentence that are `groups` groups of beam / groups rows (groups divides beam), row g·Bg + j hypothesis j of group g.  The groups pick in
+ * order; a child (h, c) of group g pays pen[n], n the rows of groups 0 … g − 1 whose live pick at this step is c (the pad of a finished
+ * parent and fill rows are not counted, eos is).  cum (in place) stays the model's sum; aug (in place, (T·beam,)) is the selection score:
+ * aug' = fp32(fp32(aug_h + step) − pen[n]), and a group's candidates — those of its own rows — rank by (double)aug' / lp[len], then the raw
+ * value, then the flat index h·C + c (h = 0 … beam − 1).  pen: beam floats, pen[n] = fp32(fp32(strength)·n), built on the host.  len is
+ * required.  groups == 1 with aug == cum is svpc_beam_step_ctl. */
+int svpc_beam_step_groups(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                          int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                          int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
+                          int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, int groups, const float* pen, float* aug,
+                          svpc_stream_t stream);
 /* end of the beam decode, n-best: per sentence its n_best (1 … beam) hypotheses in order of (double)cum / lp[len] (lp NULL: cum), ties to
  * the lower beam index; their first lt ids of `ext` into best_ids ((n_sent, n_best, lt)), cum into best_score and len into best_len
  * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */

@@ -25,50 +25,12 @@
 // history row are its ids at positions 1 … L (L + 1: its first EOS or PAD, else ld_tok − 1), BOS not a word; a gram is n consecutive
 // positions that are all words, so none spans two sentences.  Each live row's bans (its own and the history's) are merged into an LDS
 // bitmap of kBanCols bits, read only by a column that would enter a lane's top-B.
-#include "common.h"
-#include "score_row.h"
-
-#include <climits>
+#include "beam_common.h"
 
 namespace {
 
-constexpr int kBeamMax = 8;
-constexpr int kBeamThreads = 256;
 constexpr int kBanCols = 4096;                     // paragraph scope: columns of a row's ban bitmap (ops.SAMPLE_COLS_MAX)
 constexpr int kBanWords = kBanCols / 32;
-
-// insert (v, c) into the sorted top-B list (val, idx); entries past the last real one hold (-inf, INT_MAX)
-template <int B>
-__device__ __forceinline__ void topb_insert(float (&val)[B], int (&idx)[B], float v, int c) {
-    if (!raw_better(v, c, val[B - 1], idx[B - 1])) return;
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-        if (raw_better(v, c, val[k], idx[k])) {
-            const float tv = val[k]; const int ti = idx[k];
-            val[k] = v; idx[k] = c; v = tv; c = ti;
-        }
-    }
-}
-
-struct BeamArgs {
-    const float* scores; int ld; const int* row_c; const int* row_x;
-    int pos; int logits; int unk; int eos; int pad; int slot_rows;
-    float* cum; int* finished;
-    const int* text_in; const int* ext_in; const int* rows_in;
-    int* text_out; int* ext_out; int* rows_out; int ld_tok;
-    int* parent; int* next_ext; int* next_model;
-    int min_len; int ngram; const unsigned* excl; int excl_v; const double* lp; int* len;    // controls (0 / null: off)
-    const int* hist; const int* hdesc; int bos;                                            // paragraph scope (PARA only)
-};
-
-// the top-B insertion of a row with banned words (ban[0 … nb), a short LDS list): the list is read only by a column that would enter
-template <int B>
-__device__ __forceinline__ void topb_insert_ban(float (&val)[B], int (&idx)[B], float v, int c, const int* ban, int nb) {
-    if (!raw_better(v, c, val[B - 1], idx[B - 1])) return;
-    for (int k = 0; k < nb; ++k)
-        if (ban[k] == c) return;
-    topb_insert<B>(val, idx, v, c);
-}
 
 // the same with the banned words as a bitmap (paragraph scope)
 template <int B>
@@ -76,10 +38,6 @@ __device__ __forceinline__ void topb_insert_bits(float (&val)[B], int (&idx)[B],
     if (!raw_better(v, c, val[B - 1], idx[B - 1])) return;
     if (c < kBanCols && ((bits[c >> 5] >> (c & 31)) & 1u)) return;
     topb_insert<B>(val, idx, v, c);
-}
-
-__device__ __forceinline__ bool excluded(const BeamArgs& a, int y) {
-    return a.excl != nullptr && y >= 0 && y < a.excl_v && ((a.excl[y >> 5] >> (y & 31)) & 1u);
 }
 
 template <int B, bool PARA>
@@ -102,25 +60,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_kernel(BeamArgs a) {
     if (tid < NC) c_flat[tid] = INT_MAX;
     if (a.ngram == 0 || pl < a.ngram) {
         if (tid < B) n_ban[tid] = 0;
-    } else if constexpr (!PARA) {   // (block-uniform) lane l holds y_l; one lane per start j = 1 … p − n of an earlier gram
-        const int n = a.ngram, s0 = pl - n + 1;   // the (n − 1)-suffix y_{s0} … y_pos of the new gram
-        for (int h = __builtin_amdgcn_readfirstlane(wave); h < B; h += kBeamThreads / 64) {
-            if (a.finished[r0 + h]) {             // (wave-uniform; the row's wave is the only writer of n_ban[h] before the barrier)
-                if (lane == 0) n_ban[h] = 0;
-                continue;
-            }
-            const int y = lane <= a.pos ? a.ext_in[(size_t)(r0 + h) * a.ld_tok + lane] : -1;
-            const bool ex = excluded(a, y);
-            const bool suffix_ex = __ballot(ex && lane >= s0 && lane <= a.pos) != 0ull;
-            bool match = lane >= 1 && lane <= pl - n;
-            for (int k = 0; k < n - 1; ++k) match &= __shfl(y, lane + k, 64) == __shfl(y, s0 + k, 64);
-            const int w = __shfl(y, lane + n - 1, 64);
-            const bool w_ex = __shfl((int)ex, lane + n - 1, 64) != 0;
-            const bool banned = match && !suffix_ex && !w_ex;
-            const unsigned long long m = __ballot(banned);
-            if (banned) ban[h][__popcll(m & ((1ull << lane) - 1ull))] = w;
-            if (lane == 0) n_ban[h] = __popcll(m);
-        }
+    } else if constexpr (!PARA) {
+        ngram_ban_rows<B>(a, r0, pl, lane, wave, ban, n_ban);
     } else {           // paragraph scope: the row's own pass as above, then one wave-wide pass per earlier sentence, into the bitmap
         const int n = a.ngram, s0 = pl - n + 1;
         const unsigned long long gm = (1ull << n) - 1ull;      // (n <= 63)

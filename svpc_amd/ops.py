@@ -11,6 +11,7 @@ import ctypes
 import math
 import numbers
 import os
+import struct
 
 import torch
 from torch.autograd import Function as _TorchFunction
@@ -2691,6 +2692,89 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
     if history is not None:
         name, args = "beam_step_para", args + [_p(table), _p(desc.dev(dev)), int(bos)]
     _lib.call(name, *args, _stream())
+    return parent, nxt_ext, nxt
+
+
+def check_diverse(beam, num_groups, diversity_strength, n_best=None):
+    """The arguments of diverse (group) beam search, checked on the host (ValueError) → (W, G, λ as the fp32 value the table is built
+    from, n_best): W = ``beam`` 1 … BEAM_MAX, G = ``num_groups`` an integer ≥ 1 that divides W, λ = ``diversity_strength`` a finite number
+    ≥ 0, ``n_best`` 1 … W / G rows per group (None: all W / G)."""
+    W = _as_int("beam_size", beam)
+    if not 1 <= W <= BEAM_MAX:
+        raise ValueError("beam_size must be 1..%d, got %r" % (BEAM_MAX, beam))
+    G = _as_int("num_groups", num_groups)
+    if G < 1 or W % G:
+        raise ValueError("num_groups must be >= 1 and divide the beam width %d, got %d" % (W, G))
+    if isinstance(diversity_strength, bool) or not isinstance(diversity_strength, numbers.Real):
+        raise ValueError("diversity_strength must be a number, got %r" % (diversity_strength,))
+    lam = float(diversity_strength)
+    if not math.isfinite(lam) or lam < 0:
+        raise ValueError("diversity_strength must be finite and >= 0, got %r" % (diversity_strength,))
+    try:
+        lam = struct.unpack("f", struct.pack("f", lam))[0]
+    except OverflowError:
+        lam = float("inf")
+    if not math.isfinite(lam):
+        raise ValueError("diversity_strength must be finite in fp32, got %r" % (diversity_strength,))
+    k = W // G if n_best is None else _as_int("n_best", n_best)
+    if not 1 <= k <= W // G:
+        raise ValueError("n_best must be 1..%d (the rows of a group), got %d" % (W // G, k))
+    return W, G, lam, k
+
+
+def diversity_table(strength, beam):
+    """pen[n] = fp32(fp32(λ) · n) for n = 0 … ``beam`` − 1, as Python floats: what a candidate pays when n rows of earlier groups picked
+    its word at this step.  Computed once on the host; the kernel and the CPU restatement subtract the same numbers."""
+    lam = struct.unpack("f", struct.pack("f", float(strength)))[0]
+    return [struct.unpack("f", struct.pack("f", min(lam * n, 3.4028234663852886e38)))[0] for n in range(int(beam))]
+
+
+def beam_step_groups(scores, row_c, row_x, beam, groups, pos, logits, unk, eos, pad, cum, aug, finished, length, toks_in, toks_out, slot_rows,
+                     pen, *, min_length=0, block_ngram_repeat=0, exclusion=None, lp=None):
+    """One selection step of diverse (group) beam search (svpc_beam_step_groups): ``beam_step`` with controls over ``beam`` rows per
+    sentence in ``groups`` groups (row g·Bg + j: hypothesis j of group g), the groups picking in order under the Hamming penalty table
+    ``pen`` (fp32 (≥ beam,), ``diversity_table``).  In place: ``cum`` (the model's score), ``aug`` (the selection score, fp32
+    (T·beam,)), ``finished``, ``length`` (required).  → (parent, next_ext, next_model) int32 (T·beam,)."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_step_groups: beam width must be 1..%d" % BEAM_MAX)
+    if isinstance(groups, bool) or not isinstance(groups, numbers.Integral) or groups < 1 or beam % groups:
+        raise ValueError("beam_step_groups: the number of groups must divide the beam width")
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("beam_step_groups: scores must be fp32 (T·beam, C) rows with unit column stride")
+    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
+        raise ValueError("beam_step_groups: cum fp32 and finished int32, both contiguous (T·beam,)")
+    if not _row_vec(aug, R, torch.float32, scores.device) or aug.data_ptr() == cum.data_ptr():
+        raise ValueError("beam_step_groups: aug must be contiguous fp32 (T·beam,) on the scores' device, and not cum itself")
+    if pen.dtype != torch.float32 or pen.dim() != 1 or pen.shape[0] < beam or not pen.is_contiguous() or pen.device != scores.device:
+        raise ValueError("beam_step_groups: pen must be a contiguous fp32 table of >= beam entries on the scores' device")
+    lt = toks_in[0].shape[1]
+    for m in tuple(toks_in) + tuple(toks_out):
+        if not _id_rows(m, R, lt, scores.device):
+            raise ValueError("beam_step_groups: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
+    if not 0 <= pos < lt - 1 or slot_rows < lt:
+        raise ValueError("beam_step_groups: position %d outside the %d-column tables" % (pos, lt))
+    if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
+        raise ValueError("beam_step_groups: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
+    if block_ngram_repeat and lt > 64:
+        raise ValueError("beam_step_groups: block_ngram_repeat needs Lt <= 64")
+    if length is None or not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("beam_step_groups: length must be contiguous int32 (T·beam,) on the scores' device")
+    if lp is not None and not _lp_table(lp, lt, scores.device):
+        raise ValueError("beam_step_groups: lp must be a contiguous float64 table of >= Lt entries on the scores' device")
+    bits, vocab = exclusion if exclusion is not None else (None, 0)
+    if exclusion is not None and (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1
+                                  or not bits.is_contiguous() or bits.device != scores.device):
+        raise ValueError("beam_step_groups: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
+    _need_gpu(scores)
+    dev = scores.device
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("beam_step_groups", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
+              int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
+              _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
+              int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), int(groups), _p(pen), _p(aug), _stream())
     return parent, nxt_ext, nxt
 
 

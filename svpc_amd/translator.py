@@ -115,6 +115,26 @@ scores above, CIDEr by default, its idf from the plan's corpus) and the one with
 (``scope="paragraph"``: the same row k for all its sentences) or per sentence; ``translate_batch_consensus(model_inputs, plan,
 source="sample" | "nbest", num_candidates=K)`` is the decode followed by it.  On the device, without host synchronisation.
 
+**Diverse (group) beam search** (Vijayakumar et al. 2016, arXiv 1610.02424; fairseq's ``--diverse-beam-groups`` / ``-strength``, HF's
+"group beam search"): ``translate_batch_diverse(model_inputs, beam_size, num_groups, diversity_strength, n_best)`` →
+``(dec_seq_list, oov_word_dict, score_list, length_list)`` as ``translate_batch_nbest``, with K = G·n_best rows per sentence, group-major.
+Restated by tests/diverse_beam_reference.py:
+
+- the W = ``beam_size`` rows of a sentence are G = ``num_groups`` groups of Bg = W / G rows (G divides W); row g·Bg + j is hypothesis j
+  of group g; every group starts from BOS on its row 0; hypotheses never cross groups;
+- the groups pick in order at every step; a child (h, c) of group g pays pen[n] = fp32(fp32(λ)·n), λ = ``diversity_strength`` (finite,
+  ≥ 0), n the rows of groups 0 … g − 1 whose live pick at this step is the word c (Hamming diversity; the PAD of a finished parent and
+  fill rows are not counted, EOS is);
+- two scores per row: ``cum``, the model's summed step scores — what the call returns and what ``score_captions`` reproduces — and
+  ``aug``, cum minus every penalty paid, which ranks the candidates of a group: key (double)aug / lp[len], then the raw value, then the
+  flat index; the controls that work are ``min_length``, ``length_penalty_*`` and ``block_ngram_repeat`` / ``exclusion_tokens`` in sentence
+  scope (``block_ngram_scope="paragraph"`` with G > 1: ValueError);
+- at the end each group's rows are ordered by the final key (double)cum / lp[len] (the penalty steers the search, it does not judge the
+  result); the call returns ``n_best`` rows per group (1 … Bg, default Bg);
+- G = 1 is ``translate_batch_nbest(W, n_best)`` exactly; λ = 0 makes the G groups identical copies of a width-Bg beam search;
+- ``translate_batch_consensus(source="diverse", num_candidates=K, num_groups=G, diversity_strength=λ)`` decodes K / G rows per group
+  (``beam_size`` defaults to K) and picks among them.
+
 **Forced scoring** (the GOLD score / gold perplexity of the reference decoder's OpenNMT lineage):
 ``Translator.score_captions(model_inputs, dec_seq_list, unk="bar")`` scores GIVEN captions under decoding conditions (text half masked,
 ``log p`` of the mixed pointer-generator distribution).  The definition, restated by tests/forced_score_reference.py:
@@ -172,12 +192,13 @@ class Decode(object):
     checked decoding controls and their key (None: all off); ``sampling``: the checked (τ, k, q, m).  ``key`` is the decode's part of the
     plan cache key.  Outside it: ``n_best`` — the rows per sentence the call returns (0: the chosen caption alone; it only slices the
     result) — and ``seed``, this call's seed (a captured input).  FORCE (``score_captions``): ``width`` is the K given captions per
-    sentence, ``sampling`` holds (unk rule, id dtype) — part of the key — and ``given`` this call's (T, K, Lt) ids (a captured input)."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given")
+    sentence, ``sampling`` holds (unk rule, id dtype) — part of the key — and ``given`` this call's (T, K, Lt) ids (a captured input).
+    Diverse beam search: BEAM with ``groups`` = (G, fp32 λ) — part of the key; ``n_best`` is then the rows returned per group."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups")
 
-    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None):
-        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given = (
-            kind, width, controls, ctl_key, n_best, sampling, seed, given)
+    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None):
+        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups = (
+            kind, width, controls, ctl_key, n_best, sampling, seed, given, groups)
 
     @property
     def ranked(self):
@@ -186,7 +207,7 @@ class Decode(object):
 
     @property
     def key(self):
-        return (self.kind, self.width, self.ctl_key, self.ranked, self.sampling)
+        return (self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
 
 
 class DecodePlan(object):
@@ -198,6 +219,7 @@ class DecodePlan(object):
                  "ptr_hyp", "x_hyp",                            # the same, ``width`` rows per sentence: row t·width + h (incremental)
                  "controls",                                    # ranked: ops.beam_step's keywords (device tables)
                  "rounds", "rows_max",                          # paragraph scope: the round tables, the largest round's rows
+                 "groups", "pen",                               # diverse beam search: G, the device penalty table (ops.diversity_table)
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
@@ -371,6 +393,26 @@ class Translator(object):
             ops.check_paragraph_cols(self._max_cols(model_inputs))
         return self._translate(model_inputs, self.model, decode=Decode(BEAM, B, controls=ctl, ctl_key=key, n_best=n_best))
 
+    @torch.no_grad()
+    def translate_batch_diverse(self, model_inputs, beam_size=None, num_groups=None, diversity_strength=None, n_best=None, **controls):
+        """Diverse (group) beam search (module docstring): W = ``beam_size`` rows per sentence in G = ``num_groups`` groups
+        under the Hamming penalty λ = ``diversity_strength`` (defaults ``opt.beam_size``, ``opt.num_groups`` = 1,
+        ``opt.diversity_strength`` = 0.0) → (dec_seq_list, oov_word_dict, score_list, length_list): per video ids (S_b, K, Lt) int64,
+        the model score cum (S_b, K) fp32 and len (S_b, K) int64, K = G·``n_best`` rows (``n_best`` 1 … W / G per group, default all),
+        group-major, each group's rows in final-key order.  ValueError on the host for the sizes, λ, the controls and
+        ``block_ngram_scope="paragraph"`` with G > 1."""
+        W, G, lam, nb = ops.check_diverse(beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2),
+                                          num_groups if num_groups is not None else getattr(self.opt, "num_groups", 1),
+                                          diversity_strength if diversity_strength is not None else getattr(self.opt, "diversity_strength", 0.0),
+                                          n_best)
+        ctl, key = self._controls(controls)
+        if ctl["block_ngram_scope"] == "paragraph":
+            if G > 1:
+                raise ValueError("block_ngram_scope='paragraph' is not supported with num_groups > 1")
+            return self.translate_batch_nbest(model_inputs, W, nb, **controls)     # (G = 1 is the n-best decode by definition)
+        self._beam_width(W, beam_size)
+        return self._translate(model_inputs, self.model, decode=Decode(BEAM, W, controls=ctl, ctl_key=key, n_best=nb, groups=(G, lam)))
+
     SAMPLING = dict(random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0)
 
     @torch.no_grad()
@@ -502,8 +544,9 @@ class Translator(object):
     @torch.no_grad()
     def translate_batch_consensus(self, model_inputs, plan, source="sample", num_candidates=4, utility="CIDEr", scope="paragraph",
                                   weights="uniform", **decode_kw):
-        """``translate_batch_sample(num_samples=num_candidates)`` (``source="sample"``) or ``translate_batch_nbest(n_best=
-        num_candidates)`` (``"nbest"``; ``beam_size`` defaults to ``num_candidates``) followed by ``consensus`` →
+        """``translate_batch_sample(num_samples=num_candidates)`` (``source="sample"``), ``translate_batch_nbest(n_best=
+        num_candidates)`` (``"nbest"``; ``beam_size`` defaults to ``num_candidates``) or ``translate_batch_diverse(num_groups=G,
+        n_best=num_candidates / G)`` (``"diverse"``; ``beam_size`` defaults to ``num_candidates``) followed by ``consensus`` →
         (dec_seq_list, oov_word_dict, pick_list): one (S_b, Lt) int64 caption matrix per video, as greedy returns."""
         ops.check_consensus(num_candidates, utility, scope, weights)
         if source == "sample":
@@ -511,8 +554,16 @@ class Translator(object):
         elif source == "nbest":
             beam = decode_kw.pop("beam_size", num_candidates)
             dec, oov, sc, ln = self.translate_batch_nbest(model_inputs, beam, num_candidates, **decode_kw)
+        elif source == "diverse":
+            beam = decode_kw.pop("beam_size", num_candidates)
+            groups = decode_kw.pop("num_groups", getattr(self.opt, "num_groups", 1))
+            W, G, _, _ = ops.check_diverse(beam, groups, 0.0)
+            if num_candidates % G or not 1 <= num_candidates // G <= W // G:
+                raise ValueError("num_candidates must be num_groups times 1..%d rows per group, got %d with %d groups" % (W // G, num_candidates, G))
+            dec, oov, sc, ln = self.translate_batch_diverse(model_inputs, W, G, decode_kw.pop("diversity_strength", None), num_candidates // G,
+                                                            **decode_kw)
         else:
-            raise ValueError("source must be \"sample\" or \"nbest\", got %r" % (source,))
+            raise ValueError("source must be \"sample\", \"nbest\" or \"diverse\", got %r" % (source,))
         r = self.consensus(dec, plan, sc, ln, utility, scope, weights)
         return r.dec_seq_list, oov, r.pick_list
 
@@ -554,6 +605,9 @@ class Translator(object):
             if c["block_ngram_scope"] == "paragraph":
                 dp.rounds = self._paragraph_rounds(model, plan, dicts, c_list, n_oov, W, Lt, dev)
                 dp.rows_max = max(rd.n for rd in dp.rounds) * W
+        if decode.groups is not None:          # (like lp: the table lives as long as the plan and its captured graphs)
+            dp.groups = decode.groups[0]
+            dp.pen = torch.tensor(ops.diversity_table(decode.groups[1], W), dtype=torch.float32, device=dev)
         if decode.kind == SAMPLE:
             # every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed source (fixed,
             # value) and the seed the decode used are captured device words
@@ -772,7 +826,9 @@ class Translator(object):
     def _beam_search(dp, side, rows, n_sent, ptr, row_x, caches, seq_self, seq_cross, history=None):
         """The Lt − 1 selection steps of a beam decode over n_sent·B hypothesis rows, then the final pick.  The ping-pong (text ids,
         extended ids, KV-cache ancestry) pairs — children are written from their parents' rows — start with BOS and the row's own slot at
-        position 0, cum with beam 0 alone.  ``history``: ``ops.beam_step``'s, of a paragraph round."""
+        position 0, cum with beam 0 alone.  ``history``: ``ops.beam_step``'s, of a paragraph round.  Diverse beam search (``dp.groups``):
+        cum and the selection score aug start with row 0 of every group alone, the step is ``ops.beam_step_groups``, and the final
+        order is taken per group (the n-best final pick over n_sent·G "sentences" of Bg rows) → the B rows group-major."""
         cfg = side.model.config
         B, Lt, dev = dp.width, cfg.max_t_len, side.wide[0].device
         TB = n_sent * B
@@ -780,9 +836,15 @@ class Translator(object):
         toks[0][0][:, 0] = BOS
         toks[0][1][:, 0] = BOS
         toks[0][2][:, 0] = torch.arange(TB, dtype=torch.int32, device=dev) * Lt
-        cum = torch.zeros(n_sent, B, dtype=torch.float32, device=dev)
-        cum[:, 1:] = float("-inf")                                             # the first step: beam 0 alone
+        G = dp.groups
+        if G is None:
+            cum = torch.zeros(n_sent, B, dtype=torch.float32, device=dev)
+            cum[:, 1:] = float("-inf")                                         # the first step: beam 0 alone
+        else:
+            cum = torch.zeros(n_sent, G, B // G, dtype=torch.float32, device=dev)
+            cum[:, :, 1:] = float("-inf")                                      # … row 0 of every group alone
         cum = cum.view(TB)
+        aug = cum.clone() if G is not None else None
         fin = torch.zeros(TB, dtype=torch.int32, device=dev)
         nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
         length = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.ranked else None       # ranked: lengths tracked
@@ -790,8 +852,16 @@ class Translator(object):
         for i in range(Lt - 1):
             t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
             scores = side.scores(rows, ptr, nxt, i, caches, seq_self[i], seq_cross, t_in[2], B)
-            _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt, **ctl)
+            if G is None:
+                _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
+                                          **ctl)
+            else:
+                _, _, nxt = ops.beam_step_groups(scores, ptr["row_c"], row_x, B, G, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, aug, fin,
+                                                 length, t_in, t_out, Lt, dp.pen, **dp.controls)
         ext = toks[(Lt - 1) % 2][1]
+        if G is not None:    # every group's rows in final-key order
+            ids, score, ln = ops.beam_finalize_nbest(cum, ext, B // G, B // G, length, dp.controls["lp"])
+            return ids.view(n_sent, B, Lt), score.view(n_sent, B), ln.view(n_sent, B)
         if dp.ranked:        # all B hypotheses in final-key order: translate_batch_beam keeps row 0, translate_batch_nbest n_best rows
             return ops.beam_finalize_nbest(cum, ext, B, B, length, dp.controls["lp"])
         ids, score = ops.beam_finalize(cum, ext, B)
@@ -928,7 +998,14 @@ class Translator(object):
         k = decode.n_best
         res, scores, lens = [], [], []
         for plan, (ids, cum, length) in plans_outs:
-            if k:
+            if k and decode.groups is not None and k < decode.width // decode.groups[0]:      # the first k rows of every group
+                G, Bg = decode.groups[0], decode.width // decode.groups[0]
+                ids, cum, length = (v.reshape(v.shape[0], G, Bg, *v.shape[2:])[:, :, :k].reshape(v.shape[0], G * k, *v.shape[2:])
+                                    for v in (ids, cum, length))
+                length = length.to(torch.int64)
+            elif k:
+                if decode.groups is not None:
+                    k = decode.width
                 ids, cum, length = ids[:, :k], cum[:, :k], length[:, :k].to(torch.int64)
             else:
                 ids, cum, length = ids[:, 0], cum[:, 0].contiguous() if cum is not None else None, None
