@@ -667,6 +667,25 @@ int svpc_force_finish(const int* tgt, const int* len, const int* row_c, int n_ca
 int svpc_force_accum(const float* cum, const int* n_scored, const int* finished, const int* len, const int* rank, int n_cap, int lt,
                      double* acc, svpc_stream_t stream);
 
+/* ---- sequence log-likelihood of given captions as a training loss (self-critical sequence training).  Layout and the
+ *      caption's end as forced decoding above; tgt / len are svpc_force_inputs'; row_w (n_cap,) fp32 the captions' weights. */
+/* step (n_cap, lt − 1) = svpc_force_score's step under unk = "bar" (0 past the end), cum (n_cap,) = fp32(cum + step) in position order,
+ * barred (n_cap,) = 1 when a scored position's step is not finite, loss (1,) = fp32(−sum over the captions not barred of row_w·cum), the
+ * products and sums in fp64 in a fixed order.  Three launches. */
+int svpc_seq_nll_fwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const float* row_w,
+                     int n_cap, int lt, int logits, int unk, float* step, float* cum, int* barred, float* loss, svpc_stream_t stream);
+/* dscores (n_cap·lt rows of ld_out floats) = d loss / d scores times the device scalar dl (1,), every element written: 0 from column
+ * row_c[r] up, on the last position row of a caption, past its end and on every row of a barred caption; else −dl·row_w[r] / p at the target
+ * column (probabilities) or dl·row_w[r]·(softmax without unk − [c = target]), 0 at unk (logits; the log-sum-exp in fp64). */
+int svpc_seq_nll_bwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const int* barred,
+                     const float* row_w, const float* dl, int n_cap, int lt, int logits, int unk, float* dscores, int ld_out,
+                     svpc_stream_t stream);
+/* reward (n_vid, k) fp64, greedy (n_vid,) fp64 or NULL, row_vid (n_sent,) the sentences' videos -> advantage (n_vid, k) fp64 = reward −
+ * baseline (rule 0: none; 1: greedy[b]; 2: the mean of the video's other k − 1 rewards, added in ascending order) and w (n_sent·k,) fp32 =
+ * fp32(advantage[row_vid[t], k] / (n_vid·k)) at row t·k + k */
+int svpc_scst_weights(const double* reward, const double* greedy, const int* row_vid, int n_vid, int k, int n_sent, int rule,
+                      double* advantage, float* w, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

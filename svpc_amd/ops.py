@@ -1448,6 +1448,9 @@ def attention(qt, kvt, cols, D, n_heads, seq, key_mask=None, causal=False, drop=
             qt = to_f32(qt)
             kvt = qt if same else to_f32(kvt)
             split = False
+    if kvt.requires_grad and torch.is_grad_enabled() and seq.shares_keys:
+        raise _lib.SvpcKernelError("attention: sequences that share key / value rows have no backward (every sequence writes its own dK / dV "
+                                   "rows: they would be overwritten, not summed) — replicate the rows through a differentiable gather")
     out = _Attention.apply(qt, kvt, cols, D, n_heads, seq, key_mask, causal, drop)
     if split:
         out._svpc_lo = out.shape[1]
@@ -3374,3 +3377,135 @@ def force_accum(cum, n_scored, finished, length, rank, acc):
     cum, n_scored, finished, length, rank = (_c(t) for t in (cum, n_scored, finished, length, rank))
     _lib.call("force_accum", _p(cum), _p(n_scored), _p(finished), _p(length), _p(rank), R, rank.shape[-1] + 1, _p(acc), _stream())
     return acc
+
+
+# ------------------------------------------------------------------------------------------------ self-critical sequence training
+SCST_MAX = 16                   # sampled captions per sentence (what ``consensus`` and forced scoring take)
+SCST_BASELINES = ("none", "greedy", "mean")
+
+
+def check_scst(ids=None, num_samples=None, baseline="greedy", utility="CIDEr", lt=None, steps=None, weights=None):
+    """Host checks of the self-critical step (ValueError for each): ``num_samples`` K in 1 … 16; ``baseline`` "none",
+    "greedy" or "mean" (the leave-one-out mean needs K ≥ 2); ``utility`` one of the six score columns; ``ids`` the stacked captions,
+    (T, K, Lt) int32 / int64 with ``lt`` the model's Lt when given; ``steps`` the videos' sentence counts, which must add up to T;
+    ``weights`` (T, K) or (T·K,) floating point.  ``SvpcKernelError`` for ids or weights that are not on the GPU (no CPU fallback exists).
+    → (baseline rule, utility column, K)."""
+    if baseline not in SCST_BASELINES:
+        raise ValueError("baseline must be one of %s, got %r" % (", ".join(SCST_BASELINES), baseline))
+    if utility not in CONSENSUS_UTILITIES:
+        raise ValueError("utility must be one of %s, got %r" % (", ".join(CONSENSUS_UTILITIES), utility))
+    K = None
+    if num_samples is not None:
+        if isinstance(num_samples, bool) or not isinstance(num_samples, numbers.Integral) or not 1 <= int(num_samples) <= SCST_MAX:
+            raise ValueError("the self-critical step takes 1..%d samples per sentence, got K = %r" % (SCST_MAX, num_samples))
+        K = int(num_samples)
+    if ids is not None:
+        if not torch.is_tensor(ids) or ids.dim() != 3 or ids.dtype not in (torch.int32, torch.int64):
+            raise ValueError("the self-critical step takes int32 / int64 ids of shape (T, K, Lt), got %s"
+                             % ((tuple(ids.shape), ids.dtype) if torch.is_tensor(ids) else type(ids).__name__,))
+        T, k, n = ids.shape
+        if not 1 <= k <= SCST_MAX:
+            raise ValueError("the self-critical step takes 1..%d captions per sentence, got K = %d" % (SCST_MAX, k))
+        if K is not None and k != K:
+            raise ValueError("ids of %d captions per sentence, num_samples is %d" % (k, K))
+        K = k
+        if n < 2:
+            raise ValueError("captions need at least two positions (BOS and one word), got Lt = %d" % n)
+        if lt is not None and n != int(lt):
+            raise ValueError("captions of %d positions, the model's Lt is %d" % (n, lt))
+        if steps is not None and (any(int(s) < 0 for s in steps) or sum(int(s) for s in steps) != T):
+            raise ValueError("the videos' sentence counts %r do not add up to the %d caption rows given" % (list(steps), T))
+        if weights is not None and (not torch.is_tensor(weights) or not weights.is_floating_point()
+                                    or tuple(weights.shape) not in ((T, K), (T * K,))):
+            raise ValueError("weights must be floating point (%d, %d) or (%d,), got %s"
+                             % (T, K, T * K, tuple(weights.shape) if torch.is_tensor(weights) else type(weights).__name__))
+    if baseline == "mean" and K is not None and K < 2:
+        raise ValueError("baseline=\"mean\" leaves one sample out: it needs K >= 2, got K = %d" % K)
+    for t in (ids, weights):
+        if t is not None and not t.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.ops: the self-critical step runs on the GPU only (no CPU fallback exists)")
+    return SCST_BASELINES.index(baseline), CONSENSUS_UTILITIES.index(utility), K
+
+
+def scst_weights(reward, row_vid, baseline="greedy", greedy=None):
+    """Per-caption weights of the self-critical loss from per-video rewards (svpc_scst_weights, one launch, no read-back):
+    ``reward`` (N, K) float64, ``greedy`` (N,) float64 (``baseline="greedy"`` only), ``row_vid`` the T sentences' video index (an Idx or
+    host ints) → (advantage (N, K) float64 = reward − baseline, w (T·K,) fp32 = fp32(advantage[vid(t), k] / (N·K)) at row t·K + k)."""
+    if not torch.is_tensor(reward) or reward.dim() != 2 or reward.dtype != torch.float64:
+        raise ValueError("scst_weights: reward must be float64 (N, K)")
+    N, K = reward.shape
+    rule, _, _ = check_scst(num_samples=K, baseline=baseline)
+    if rule == 1:
+        if not torch.is_tensor(greedy) or greedy.dtype != torch.float64 or tuple(greedy.shape) != (N,) or greedy.device != reward.device:
+            raise ValueError("scst_weights: baseline=\"greedy\" needs the greedy rewards, float64 (%d,) on the rewards' device" % N)
+    else:
+        greedy = None
+    rv = as_idx(row_vid)
+    if any(not 0 <= b < N for b in rv.host):
+        raise ValueError("scst_weights: a sentence's video index lies outside the %d videos" % N)
+    _need_gpu(reward)
+    reward = _c(reward)
+    greedy = _c(greedy) if greedy is not None else None
+    dev, T = reward.device, len(rv.host)
+    adv = torch.empty(N, K, dtype=torch.float64, device=dev)
+    w = torch.empty(T * K, dtype=torch.float32, device=dev)
+    _lib.call("scst_weights", _p(reward), _p(greedy), _p(rv.dev(dev)) if T else None, N, K, T, rule, _p(adv), _p(w), _stream())
+    return adv, w
+
+
+class _SeqNll(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, row_w, logits, unk_id, max_c):
+        R, lt = tgt.shape
+        dev = scores.device
+        step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        cum = torch.empty(R, dtype=torch.float32, device=dev)
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_nll_fwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(row_w), R, lt, logits, unk_id,
+                  _p(step), _p(cum), _p(barred), _p(loss), _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, row_w)
+        ctx.cfg = (R, lt, logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 8
+        scores, rc, tgt, length, barred, row_w = ctx.saved_tensors
+        R, lt, logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        _lib.call("seq_nll_bwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(row_w), _p(dl), R, lt,
+                  logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return dscores, None, None, None, None, None, None, None
+
+
+def seq_nll(scores, row_c, tgt, length, row_w, logits, unk_id, max_cols=None):
+    """The weighted sequence log-likelihood loss of given captions from the decoder's score matrix (svpc_seq_nll_fwd / _bwd; DESIGN
+    §11.10), differentiable in ``scores`` only: ``scores`` (≥ R·Lt, ≥ C) fp32 — row r·Lt + i is step i of caption row r; probabilities, or
+    logits when ``logits`` —, ``row_c`` the R rows' column counts (an Idx or host ints), ``tgt`` (R, Lt) / ``length`` (R,) int32 as
+    ``force_inputs`` returns them, ``row_w`` (R,) fp32 weights → (loss () fp32 = −Σ w_r·cum_r over the captions that are not barred, cum
+    (R,) fp32, step (R, Lt − 1) fp32 — ``force_score``'s under ``unk="bar"`` —, barred (R,) int32: a scored position without a finite step
+    score; such a caption adds nothing to the loss and gets an exactly zero gradient)."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_nll: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_nll: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_nll: length must be contiguous int32 (R,) on the scores' device")
+    if not _row_vec(row_w, R, torch.float32, scores.device):
+        raise ValueError("seq_nll: row_w must be contiguous fp32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_nll: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_nll: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    _need_gpu(scores)
+    return _SeqNll.apply(_c(scores), rc.dev(scores.device), tgt, length, row_w, 1 if logits else 0, int(unk_id), max_c)

@@ -160,6 +160,21 @@ class SeqInfo:
         self.max_q, self.max_k = max(self.h_q_len), max(self.h_k_len)
         self.n_q_rows = max(o + l for o, l in zip(self.h_q_off, self.h_q_len))
         self.n_k_rows = max(o + l for o, l in zip(self.h_k_off, self.h_k_len))
+        self._shares_keys = None
+
+    @property
+    def shares_keys(self):
+        """two sequences read a common key row (the K hypotheses of a sentence over its memory rows): fine without gradients; the
+        attention backward writes every sequence's own dK / dV rows, so such rows would be overwritten instead of summed"""
+        if self._shares_keys is None:
+            end, shared = 0, False
+            for o, l in sorted(zip(self.h_k_off, self.h_k_len)):
+                if l > 0 and o < end:
+                    shared = True
+                    break
+                end = max(end, o + l)
+            self._shares_keys = shared
+        return self._shares_keys
 
     @classmethod
     def uniform(cls, n, lq, lk, device="cpu"):
