@@ -18,6 +18,10 @@ from torch.autograd import Function as _TorchFunction
 
 from . import _lib
 from .ops_common import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, FIdx, Idx, SeqInfo, as_idx  # noqa: F401
+# The tail of backward — deferred parameter-gradient work (grouped weight gradients, bias column sums, reduction finalizers), the
+# gradient-ready notifications and the end-of-backward join — lives in grad_tail.py; its public names are re-exported here.
+from .grad_tail import (HOOKS_PAUSED, _WgradProblem, _queue_end_of_backward_join, _ready, bias_grad, defer_colsum,  # noqa: F401
+                        defer_finalize, defer_partials, defer_wgrad, flush_finalizes, flush_pending, flush_wgrads, hooks_paused, join_side)
 
 _WS = {}
 _WS_BYTES = 256 << 20
@@ -62,292 +66,7 @@ def _ws(device):
     return w
 
 
-# Side streams for parameter gradients (OFF by default, SVPC_SIDE=1 / SVPC_BRANCH=1 enable them): a weight / bias gradient written
-# straight into the optimizer's arena has no consumer until the optimizer (or the gradient all-reduce) runs, so its kernels can be
-# forked onto a side stream and run beside the dgrad chain.  Measured: this won 6 % while the side kernels were slow and numerous;
-# since the finalizers / column sums were rewritten and the weight gradients grouped, the captured graph replays 3 % FASTER as one
-# linear chain — the graph executor spreads a forked graph over four hardware queues and a main-chain kernel then waits behind
-# unrelated side work that happens to share its queue (gaps of 20–80 µs in the kernel trace).  A gradient always uses the same
-# side stream (accumulating launches stay ordered); the streams are joined at the end of backward (autograd callback), before a
-# gradient bucket is all-reduced, and before the optimizer kernels.  Inside a hipGraph capture the forks/joins become edges.
-SIDE_WGRAD = os.environ.get("SVPC_SIDE", "") != ""
-_N_SIDE = int(os.environ.get("SVPC_N_SIDE", "2"))
-_SIDE = {}
-_SIDE_DIRTY = []
-_JOIN_QUEUED = [False]
-
-
-_BRANCH = {}
-BRANCH_STREAMS = os.environ.get("SVPC_BRANCH", "") != ""
-
-
-def branch_stream(device):
-    """Stream for an independent forward branch (its autograd nodes run their backward there too); None when disabled."""
-    if not BRANCH_STREAMS:
-        return None
-    st = _BRANCH.get(device)
-    if st is None:
-        st = _BRANCH[device] = torch.cuda.Stream(device=device)
-    return st
-
-
-# Grouped weight gradients: the wgrad (+ bias gradient) of an fp32-storage linear whose gradients go straight to the arena is not
-# launched in its backward but queued; the queue is flushed as ONE grouped launch (svpc_gemm_group_wgrad) on a side stream when it
-# is full, when a queued target would be written twice, and at every join point (end of backward, before a gradient bucket is
-# all-reduced, before the optimizer).  ≈50 text-side / step-level linears per step × 3 launches (wgrad, column sum, finalize) of
-# ≈5–15 µs each become 2–3 launches.
-USE_GROUPED_WGRAD = os.environ.get("SVPC_NO_GROUPED_WGRAD", "") == ""
-GROUP_BF16 = os.environ.get("SVPC_NO_GROUP_BF16", "") == ""      # also the bf16-stream wgrads (one launch, no split-K)
-GROUP_FLUSH_AT = int(os.environ.get("SVPC_GROUP_FLUSH_AT", "16"))
-# packed Q/K/V (432 tiles of 64²) and LSTM (576) weight gradients over K = 192 rows are pure latency as launches of their own
-GROUP_MAX_TILES = int(os.environ.get("SVPC_GROUP_MAX_TILES", "1200"))
-_WQ = []            # (dz, x, wgrad, bgrad)
-
-
-class _WgradProblem(ctypes.Structure):
-    _fields_ = [("dz", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("db", ctypes.c_void_p),
-                ("n_out", ctypes.c_int), ("n_in", ctypes.c_int), ("rows", ctypes.c_int), ("ld_dz", ctypes.c_int),
-                ("ld_x", ctypes.c_int), ("ld_dw", ctypes.c_int)]
-
-
-def _queue_end_of_backward_join():
-    if not _JOIN_QUEUED[0]:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(join_side)
-            _JOIN_QUEUED[0] = True
-        except RuntimeError:      # not inside a backward pass: the caller joins (optimizer / reducer do)
-            pass
-
-
-_WQ16 = []          # bf16-stream problems (dz, x, wgrad, None): one launch at the join points, whole k-loop per tile
-
-
 P8W_BIAS = os.environ.get("SVPC_NO_P8W_BIAS", "") == ""      # bias gradients of the bf16-stream linears inside the grouped wgrad launch
-
-
-def _defer_wgrad16(dz, x, wgrad, bgrad=None):
-    rows, n_out = dz.shape
-    n_in = x.shape[1]
-    if n_out % 8 or n_in % 8 or dz.stride(0) % 8 or x.stride(0) % 8 or wgrad.stride(0) % 4 or rows < 1:
-        return False
-    if (dz.data_ptr() | x.data_ptr()) % 16 or dz.stride(1) != 1 or x.stride(1) != 1 or not wgrad.is_contiguous():
-        return False
-    wp = wgrad.data_ptr()
-    bp = bgrad.data_ptr() if bgrad is not None else -1
-    if any(q[2].data_ptr() == wp or (q[3] is not None and q[3].data_ptr() == bp) for q in _WQ16) or \
-            len(_WQ16) >= _lib.load().svpc_gemm_group_wgrad_max():
-        flush_wgrads()
-    _WQ16.append((dz, x, wgrad, bgrad))
-    _queue_end_of_backward_join()
-    return True
-
-
-def defer_wgrad(dz, x, wgrad, bgrad):
-    """Queue dW += dzᵀ·x (and db += Σ dz) for the grouped launch; False if this problem must be launched on its own."""
-    if USE_GROUPED_WGRAD and GROUP_BF16 and _fast() and wgrad is not None and not SIDE_WGRAD and \
-            dz.dtype == torch.bfloat16 and x.dtype == torch.bfloat16:
-        return _defer_wgrad16(dz, x, wgrad, bgrad)
-    if not (USE_GROUPED_WGRAD and _fast() and wgrad is not None and dz.dtype == torch.float32 and x.dtype == torch.float32) or BWD_EXACT:
-        return False
-    rows, n_out = dz.shape
-    n_in = x.shape[1]
-    if rows < 1 or n_out % 4 or n_in % 4 or dz.stride(0) % 4 or x.stride(0) % 4 or wgrad.stride(0) % 4:      # any row count: k tail zero-sourced
-        return False
-    if (dz.data_ptr() | x.data_ptr()) % 16 or dz.stride(1) != 1 or x.stride(1) != 1 or not wgrad.is_contiguous():
-        return False
-    tiles = -(-n_out // 64) * -(-n_in // 64)
-    if tiles > GROUP_MAX_TILES:   # a grid of its own fills the chip for long enough: nothing to gain from grouping
-        return False
-    wp = wgrad.data_ptr()
-    if any(q[2].data_ptr() == wp for q in _WQ):
-        flush_wgrads(bf16=False)  # two accumulations into one gradient stay ordered
-    _WQ.append((dz, x, wgrad, bgrad))
-    if len(_WQ) >= min(GROUP_FLUSH_AT, _lib.load().svpc_gemm_group_wgrad_max()):
-        flush_wgrads(bf16=False)
-    _queue_end_of_backward_join()
-    return True
-
-
-def flush_wgrads(bf16=True):
-    if _WQ16 and bf16:
-        probs = (_WgradProblem * len(_WQ16))()
-        for i, (dz, x, wg, bg) in enumerate(_WQ16):
-            probs[i] = _WgradProblem(dz.data_ptr(), x.data_ptr(), wg.data_ptr(), bg.data_ptr() if bg is not None else None, dz.shape[1],
-                                     x.shape[1], dz.shape[0], dz.stride(0), x.stride(0), wg.stride(0))
-        ws = _ws(_WQ16[0][0].device)
-        # the 8-phase template with transposed fragment reads when every problem is at least 256 wide (gemm_p8w.hip: it also takes the
-        # bias gradients from the dz tiles it stages), else the round-1 form with the column sums as a pass of their own
-        p8w = USE_P8W and _lib.load().svpc_gemm_group_wgrad_bf16_p8_ok(ctypes.addressof(probs), len(_WQ16)) == 1
-        done = list(_WQ16)
-        del _WQ16[:]
-        if not p8w:
-            for i, (dz, x, wg, bg) in enumerate(done):
-                if bg is not None:
-                    probs[i].db = None
-                    defer_colsum(dz, bg)
-        _lib.call("gemm_group_wgrad_bf16_p8" if p8w else "gemm_group_wgrad_bf16_ws", ctypes.addressof(probs), len(done), _p(ws),
-                  ws.numel() * 4, _stream())
-        for _, _, wg, bg in done:
-            _ready(wg, "w")
-            if bg is not None and p8w:
-                _ready(bg, "b")
-    if not _WQ:
-        return
-    dev = _WQ[0][0].device
-    pool = _SIDE.get(dev)
-    if pool is None:
-        pool = _SIDE[dev] = [torch.cuda.Stream(device=dev) for _ in range(_N_SIDE)]
-    side = pool[0] if SIDE_WGRAD else torch.cuda.current_stream()
-    probs = (_WgradProblem * len(_WQ))()
-    for i, (dz, x, wg, bg) in enumerate(_WQ):
-        probs[i] = _WgradProblem(dz.data_ptr(), x.data_ptr(), wg.data_ptr(), bg.data_ptr() if bg is not None else None,
-                                 dz.shape[1], x.shape[1], dz.shape[0], dz.stride(0), x.stride(0), wg.stride(0))
-    if SIDE_WGRAD:
-        side.wait_stream(torch.cuda.current_stream())
-        for dz, x, _, _ in _WQ:
-            dz.record_stream(side); x.record_stream(side)
-        if side not in _SIDE_DIRTY:
-            _SIDE_DIRTY.append(side)
-    _lib.call("gemm_group_wgrad", ctypes.addressof(probs), len(_WQ), side.cuda_stream)
-    done = list(_WQ)
-    del _WQ[:]
-    for _, _, wg, bg in done:
-        _ready(wg, "w")
-        if bg is not None:
-            _ready(bg, "b")
-
-
-# Deferred reduction tails: the second stage of every bias-gradient column sum and of every LayerNorm gain/shift gradient (≈90 per
-# step, 5–6 µs each, a few KB of work) is queued and run as ONE table-driven launch (svpc_multi_finalize) at the join points.
-USE_MULTI_FINALIZE = os.environ.get("SVPC_NO_MULTI_FINALIZE", "") == ""
-GROUP_COLSUM = os.environ.get("SVPC_NO_GROUP_COLSUM", "") == ""
-_FQ = []            # (partial, out0, out1, groups, ncols, split)
-
-
-class _FinalizeEntry(ctypes.Structure):
-    _fields_ = [("partial", ctypes.c_void_p), ("out0", ctypes.c_void_p), ("out1", ctypes.c_void_p), ("groups", ctypes.c_int),
-                ("ncols", ctypes.c_int), ("split", ctypes.c_int)]
-
-
-def defer_finalize(partial, groups, ncols, out0, out1=None, split=None):
-    """out0/out1 (+)= column sums of ``partial`` (groups × ncols), later, together with every other pending tail"""
-    tgt = (out0.data_ptr(), out1.data_ptr() if out1 is not None else 0)
-    if any(q[1].data_ptr() in tgt or (q[2] is not None and q[2].data_ptr() in tgt) for q in _FQ):
-        flush_finalizes()
-    _FQ.append((partial, out0, out1, int(groups), int(ncols), int(ncols if split is None else split)))
-    if len(_FQ) >= _lib.load().svpc_multi_finalize_max():
-        flush_finalizes()
-    _queue_end_of_backward_join()
-
-
-_CQ = []            # pending first stages of bias-gradient column sums: (x, partial)
-
-
-class _ColsumEntry(ctypes.Structure):
-    _fields_ = [("x", ctypes.c_void_p), ("partial", ctypes.c_void_p), ("dt", ctypes.c_int), ("ldx", ctypes.c_int), ("R", ctypes.c_int),
-                ("C", ctypes.c_int)]
-
-
-def defer_colsum(x, out):
-    """out += Σ_rows x, both stages deferred: the column sums of all pending tensors run as one launch, then the finalizes"""
-    R, C = x.shape
-    partial = torch.empty(_lib.load().svpc_colsum_chunks(R) * C, dtype=torch.float32, device=x.device)
-    if len(_CQ) >= 48:
-        flush_finalizes()
-    _CQ.append((x, partial))
-    defer_finalize(partial, _lib.load().svpc_colsum_chunks(R), C, out)
-
-
-def _flush_colsums():
-    if not _CQ:
-        return
-    ents = (_ColsumEntry * len(_CQ))()
-    for i, (x, partial) in enumerate(_CQ):
-        ents[i] = _ColsumEntry(x.data_ptr(), partial.data_ptr(), _dt(x), x.stride(0), x.shape[0], x.shape[1])
-    _lib.call("multi_colsum", ctypes.addressof(ents), len(_CQ), _stream())
-    del _CQ[:]
-
-
-def flush_finalizes():
-    _flush_colsums()
-    if not _FQ:
-        return
-    ents = (_FinalizeEntry * len(_FQ))()
-    for i, (partial, o0, o1, g, nc, sp) in enumerate(_FQ):
-        ents[i] = _FinalizeEntry(partial.data_ptr(), o0.data_ptr(), (o1 if o1 is not None else o0).data_ptr(), g, nc, sp)
-    _lib.call("multi_finalize", ctypes.addressof(ents), len(_FQ), _stream())
-    done = list(_FQ)
-    del _FQ[:]
-    for _, o0, o1, _, _, _ in done:
-        _ready(o0, "b" if o1 is None else None)
-        if o1 is not None:
-            _ready(o1)
-
-
-def flush_pending():
-    """Launch every queued gradient tail (grouped wgrads, column sums, finalizers) and make the current stream wait for the side
-    streams that carry gradient work.  Safe at any point of a backward pass: parked residual gradients (``_RES_SINK``) are left
-    alone — LayerNorm backwards legitimately keep one parked until the consuming projection's dgrad runs."""
-    flush_wgrads()
-    flush_finalizes()
-    if _SIDE_DIRTY:
-        cur = torch.cuda.current_stream()
-        for st in _SIDE_DIRTY:
-            cur.wait_stream(st)
-        del _SIDE_DIRTY[:]
-
-
-def join_side():
-    """End of a backward pass (autograd callback) / before the optimizer kernels: ``flush_pending`` + the leftover check of the
-    residual-gradient hand-over.  NOT for use in the middle of backward (a gradient bucket released by a hook calls
-    ``flush_pending``): a parked gradient is normal there."""
-    flush_pending()
-    _JOIN_QUEUED[0] = False
-    if _RES_SINK:
-        n_left = len(_RES_SINK)
-        _RES_SINK.clear()
-        raise _lib.SvpcKernelError("residual-gradient hand-over: %d parked gradient(s) were never absorbed by a projection's dgrad "
-                                   "(layernorm(..., sink=True) without a consuming ops.linear)" % n_left)
-
-
-class _side_of:
-    """``with _side_of(grad, dz, x):`` — launches inside run on the side stream that owns arena gradient ``grad``; the listed
-    tensors are produced on the current stream and read there."""
-
-    def __init__(self, grad, *tensors):
-        self.on = SIDE_WGRAD and grad is not None and grad.is_cuda
-        if not self.on:
-            return
-        dev = grad.device
-        pool = _SIDE.get(dev)
-        if pool is None:
-            pool = _SIDE[dev] = [torch.cuda.Stream(device=dev) for _ in range(_N_SIDE)]
-        self.stream = pool[(grad.data_ptr() >> 9) % len(pool)]
-        self.tensors = tensors
-
-    def __enter__(self):
-        if not self.on:
-            return self
-        self.stream.wait_stream(torch.cuda.current_stream())
-        for t in self.tensors:
-            if t is not None:
-                t.record_stream(self.stream)
-        if self.stream not in _SIDE_DIRTY:
-            _SIDE_DIRTY.append(self.stream)
-        if not _JOIN_QUEUED[0]:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(join_side)
-                _JOIN_QUEUED[0] = True
-            except RuntimeError:      # not inside a backward pass: the caller joins (optimizer / reducer do)
-                pass
-        self.cm = torch.cuda.stream(self.stream)
-        self.cm.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.cm.__exit__(*exc)
-        return False
 
 
 def _need_gpu(t):
@@ -808,7 +527,6 @@ def _colsum(x2d, idx=None, K=1, out=None, accumulate=0):
 # Direct-to-arena parameter gradients: once the optimizer has re-pointed ``p.grad`` into its contiguous arena (and marked
 # the parameter), backward kernels accumulate weight / bias / gain gradients straight into that storage (GEMM epilogue
 # ``accumulate``, reduction finalizers) instead of returning a tensor for autograd to add — no temporaries, no add kernels.
-GRAD_READY_HOOK = None     # set by GradReducer: called with the data_ptr of every arena gradient that has just been written
 
 
 def _direct(p):
@@ -823,27 +541,6 @@ def direct_grads(*params):
     bias that is a sum of parameters"""
     gs = tuple(_direct(p) for p in params)
     return gs if all(g is not None for g in gs) else None
-
-
-HOOKS_PAUSED = [0]         # > 0: gradient-ready notifications (pointer reports here, the reducer's post-accumulate hooks) are ignored
-
-
-class hooks_paused:
-    """``with ops.hooks_paused():`` — while a part of the step is warmed up / captured into a hipGraph (svpc_amd/clip_graphs.py) the
-    data-parallel reducer must not count the parameter writes of that pass (nor issue a collective from inside a capture)."""
-
-    def __enter__(self):
-        HOOKS_PAUSED[0] += 1
-        return self
-
-    def __exit__(self, *exc):
-        HOOKS_PAUSED[0] -= 1
-        return False
-
-
-def _ready(t, kind=None):
-    if GRAD_READY_HOOK is not None and t is not None and not HOOKS_PAUSED[0]:
-        GRAD_READY_HOOK(t.data_ptr(), t.numel(), kind)
 
 
 def _shadow(w):
@@ -971,13 +668,7 @@ class _Linear(Function):
             # the bias is the sum of several parameters (the LSTM's b_ih + b_hh, model.py:1022): each of them receives Σ_rows dz in place —
             # the first the usual way below, the others through one more entry of the grouped column sum
             for e in bgrad[1:]:
-                V = 8 if dz.dtype == torch.bfloat16 else 4
-                if USE_MULTI_FINALIZE and not SIDE_WGRAD and N % V == 0 and dz.stride(0) % V == 0 and dz.data_ptr() % 16 == 0 and M > 0:
-                    defer_colsum(dz, e)
-                else:
-                    with _side_of(e, dz):
-                        _colsum(dz, out=e.view(1, -1), accumulate=1)
-                    _ready(e, "b")
+                bias_grad(dz, e)
             bgrad = bgrad[0]
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, dtype=x.dtype, device=dy.device)
@@ -1006,29 +697,16 @@ class _Linear(Function):
         if not w_done and (wgrad is not None or ctx.needs_input_grad[1]):
             acc = 1 if wgrad is not None else 0
             dw = wgrad if wgrad is not None else torch.empty_like(w)
-            with _side_of(wgrad, dz, x):
-                if trans_w:   # w (K, N): dw = xᵀ dz
-                    _gemm(x, x.stride(0), 0, dz, N, 0, dw, K, N, M, accumulate=acc)
-                else:         # w (N, K): dw = dzᵀ x
-                    _gemm(dz, N, 0, x, x.stride(0), 0, dw, N, K, M, accumulate=acc)
+            if trans_w:   # w (K, N): dw = xᵀ dz
+                _gemm(x, x.stride(0), 0, dz, N, 0, dw, K, N, M, accumulate=acc)
+            else:         # w (N, K): dw = dzᵀ x
+                _gemm(dz, N, 0, x, x.stride(0), 0, dw, N, K, M, accumulate=acc)
             if wgrad is not None:
                 _ready(wgrad, "w")
                 dw = None
         if has_b and (bgrad is not None or ctx.needs_input_grad[2]):
             if bgrad is not None:
-                V = 8 if dz.dtype == torch.bfloat16 else 4
-                if (USE_MULTI_FINALIZE and not SIDE_WGRAD and N % V == 0 and dz.stride(0) % V == 0 and dz.data_ptr() % 16 == 0 and M > 0):
-                    if GROUP_COLSUM:
-                        defer_colsum(dz, bgrad)
-                    else:
-                        chunks = _lib.load().svpc_colsum_chunks(M)
-                        partial = torch.empty(chunks * N, dtype=torch.float32, device=dz.device)
-                        _lib.call("colsum_partial_t", _p(dz), _dt(dz), dz.stride(0), M, N, _p(partial), _stream())
-                        defer_finalize(partial, chunks, N, bgrad)
-                else:
-                    with _side_of(bgrad, dz):
-                        _colsum(dz, out=bgrad.view(1, -1), accumulate=1)
-                    _ready(bgrad, "b")
+                bias_grad(dz, bgrad)
             else:
                 db = _colsum(dz).view(-1)
         return dx, dw, db, None, None, None, None, None, None, None, None
@@ -1181,25 +859,17 @@ class _LayerNorm(Function):
         if need_x:
             dx_rows = dh if (p_pre <= 0.0 and same_t) else torch.empty(R, D, dtype=x.dtype, device=dev)
         g_dir, b_dir, x_dir, a2_dir = ctx.direct
-        direct_gb = g_dir is not None and b_dir is not None
-        dgamma = g_dir if direct_gb else torch.empty(D, dtype=torch.float32, device=dev)
-        dbeta = b_dir if direct_gb else torch.empty(D, dtype=torch.float32, device=dev)
-        # rows part on this stream; the dgamma/dbeta tail only feeds the optimizer, so it is forked off (own partial buffer)
+        # the dgamma/dbeta tail only feeds the optimizer: per-group partials now, their column sums with every other pending tail
         groups = (_lib.load().svpc_ln_param_only_groups(R) if dh is None and dx_rows is None else _lib.load().svpc_ln_bwd_groups(R))
         partial = torch.empty(groups * 2 * D, dtype=torch.float32, device=dev)
         # (strided form: in bf16x3 mode the saved x / residual are the hi planes of split rows, read in place)
         _lib.call("ln_bwd_rows_s", _p(dy), _p(x), _dt(x), x.stride(0), _dt(dy), _p(src_rows), _p(residual),
                   residual.stride(0) if residual is not None else 0, _p(gamma), _p(mean), _p(rstd), _p(dh), _p(dx_rows), _p(partial), R, D,
                   p_pre, s_pre, p_post, s_post, _p(seed), _stream())
-        if direct_gb and USE_MULTI_FINALIZE and not SIDE_WGRAD:
-            defer_finalize(partial, groups, 2 * D, dgamma, dbeta, D)
-            dgamma = dbeta = None
-        else:
-            with _side_of(g_dir if direct_gb else None, partial):
-                _lib.call("ln_param_grads_g", _p(partial), groups, D, _p(dgamma), _p(dbeta), 1 if direct_gb else 0, _stream())
-            if direct_gb:
-                _ready(dgamma); _ready(dbeta)
-                dgamma = dbeta = None
+        dgamma = dbeta = None
+        if not defer_partials(partial, groups, 2 * D, g_dir, b_dir, D):
+            dgamma, dbeta = torch.empty(D, dtype=torch.float32, device=dev), torch.empty(D, dtype=torch.float32, device=dev)
+            _lib.call("ln_param_grads_g", _p(partial), groups, D, _p(dgamma), _p(dbeta), 0, _stream())
         dx = None
         if need_x:
             if src_rows is not None:
@@ -1635,9 +1305,7 @@ class _CrossAttnLn(Function):
                   _p(part_ln), T, lt, nm, D, H, scale, p, site, _p(seed), _p(ro), _p(rl), _stream())
         g_d, b_d = ctx.direct
         dgamma = dbeta = None
-        if g_d is not None and b_d is not None and USE_MULTI_FINALIZE and not SIDE_WGRAD:
-            defer_finalize(part_ln, T, 2 * D, g_d, b_d, D)
-        else:
+        if not defer_partials(part_ln, T, 2 * D, g_d, b_d, D):
             sl = _colsum(part_ln).view(-1)
             dgamma, dbeta = sl[:D].clone(), sl[D:].clone()
             if g_d is not None:
@@ -1907,9 +1575,9 @@ class _SimHeads(Function):
         p4 = torch.empty(G, Wd + 1, dtype=torch.float32, device=dev)
         _lib.call("sim_heads_bwd", _p(hh), _p(fb), _p(W3), _p(W4), _p(c), _p(dc), _p(dw), _p(dhh), _p(dfb), _p(p3), _p(p4), T, D, Wd, _stream())
         w3d, b3d, w4d, b4d = ctx.direct
-        if all(t is not None for t in ctx.direct) and USE_MULTI_FINALIZE and not SIDE_WGRAD:
-            defer_finalize(p3, G, 3 * D + 3, w3d, b3d, 3 * D)
-            defer_finalize(p4, G, Wd + 1, w4d, b4d, Wd)
+        if all(t is not None for t in ctx.direct):
+            defer_partials(p3, G, 3 * D + 3, w3d, b3d, 3 * D)
+            defer_partials(p4, G, Wd + 1, w4d, b4d, Wd)
             return dhh, dfb, None, None, None, None
         s3, s4 = _colsum(p3).view(-1), _colsum(p4).view(-1)
         outs = [s3[:3 * D].reshape(3, D), s3[3 * D:].clone(), s4[:Wd].reshape(1, Wd), s4[Wd:].clone()]
@@ -2004,9 +1672,7 @@ class _PtrAttnGate(Function):
                   _p(dbank), _p(wpart), T, lt, e_max, D, _p(ro), _p(rl), _stream())
         wg, bg = ctx.direct
         dw = db = None
-        if wg is not None and bg is not None and USE_MULTI_FINALIZE and not SIDE_WGRAD:
-            defer_finalize(wpart, T, 2 * D + 1, wg, bg, 2 * D)       # (column sums of the per-step partials, with every other pending tail)
-        else:
+        if not defer_partials(wpart, T, 2 * D + 1, wg, bg, 2 * D):      # (else: with every other pending tail)
             sums = _colsum(wpart).view(-1)
             dw, db = sums[:2 * D].reshape(1, 2 * D), sums[2 * D:]
             if wg is not None:
@@ -2229,8 +1895,7 @@ class _LstmSeq(Function):
         if wgrad is not None or ctx.needs_input_grad[1]:
             acc = 1 if wgrad is not None else 0
             dw = wgrad if wgrad is not None else torch.empty_like(w)
-            with _side_of(wgrad, dG2, hp):
-                _gemm(dG2, 4 * D, 0, hp, D, 0, dw, 4 * D, D, S * N, accumulate=acc)
+            _gemm(dG2, 4 * D, 0, hp, D, 0, dw, 4 * D, D, S * N, accumulate=acc)
             if wgrad is not None:
                 _ready(wgrad, "w")
                 dw = None

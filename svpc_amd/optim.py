@@ -16,7 +16,7 @@ import re
 
 import torch
 
-from . import _lib
+from . import _lib, grad_tail
 
 NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight")  # src/train.py:339
 
@@ -356,7 +356,7 @@ class FusedBertAdam:
         from . import clip_graphs, ops
         clip_graphs.check_consumed()  # (a replayed clip-encoder forward whose backward replay was never requested: loud, not silent)
         WEIGHTS_EPOCH[0] += 1         # (the kernels rewrite the parameters behind autograd's version counters)
-        ops.join_side()        # parameter-gradient kernels forked onto side streams
+        ops.join_side()        # parameter-gradient work still queued (grouped wgrads, column sums, finalizers) goes first
         stream = torch.cuda.current_stream().cuda_stream
         _lib.call("opt_step", self.meta.data_ptr(), self.chunk_tid.data_ptr(), self.chunk_start.data_ptr(),
                   self.tensor_chunk_off.data_ptr(), self.n_tensors, self.n_chunks, self.partial.data_ptr(),
@@ -430,7 +430,6 @@ class GradReducer:
         self._handles = []
         self._by_pack = {}
         if self.overlap:
-            from . import ops
             bucket_of = {}
             for bi, (s, e, members) in enumerate(self.buckets):
                 for i in members:
@@ -442,7 +441,7 @@ class GradReducer:
             # that) — so it is the "last write has been enqueued or queued" signal, multi-use parameters included; the queues are
             # flushed before a bucket is exchanged (``_launch``).  (2) Packed Q/K/V (K/V) projections use views of the weight
             # store that have no autograd edge to their member parameters: their in-place writes are reported by pointer
-            # (``ops._ready`` → ``_ready_ptr``), one write per view and step.
+            # (``grad_tail._ready`` → ``_ready_ptr``), one write per view and step.
             for i, p in enumerate(arena.params):
                 packed = getattr(p, "_svpc_packed", None)
                 if packed is not None:
@@ -458,7 +457,7 @@ class GradReducer:
                     wi, bi = p._svpc_stack_members
                     self._by_pack[("w", stack[0].data_ptr(), stack[0].numel())] = [(j, bucket_of[j]) for j in wi]
                     self._by_pack[("b", stack[1].data_ptr(), stack[1].numel())] = [(j, bucket_of[j]) for j in bi]
-            ops.GRAD_READY_HOOK = self._ready_ptr
+            grad_tail.GRAD_READY_HOOK = self._ready_ptr
         self.reset()
 
     def _close(self, members):
@@ -513,19 +512,18 @@ class GradReducer:
 
     def close(self):
         """remove the hooks (tests; a reducer normally lives as long as the model)"""
-        from . import ops
         for h in self._handles:
             h.remove()
         self._handles = []
-        if ops.GRAD_READY_HOOK == self._ready_ptr:
-            ops.GRAD_READY_HOOK = None
+        if grad_tail.GRAD_READY_HOOK == self._ready_ptr:
+            grad_tail.GRAD_READY_HOOK = None
 
     def _launch(self, bi):
         from . import ops
         self.launched[bi] = True     # first: flushing the queues below reports more gradients ready (re-entrant)
         self._in_launch += 1         # (those reports may name members of buckets already released by their hooks: the same write,
         try:                         #  seen by hook and by pointer — expected; only a report OUTSIDE a flush is a second write)
-            ops.flush_pending()      # the bucket's gradients may still sit in a deferred-tail queue or on a side stream
+            ops.flush_pending()      # the bucket's gradients may still sit in a deferred-tail queue
         finally:
             self._in_launch -= 1
         s, e, _ = self.buckets[bi]

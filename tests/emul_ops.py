@@ -322,10 +322,6 @@ def bilstm_sequences(gx_f, gx_b, w_f, w_b, rows_f, rows_b, active_t, pick_f, pic
     return of + ob if summed else (of, ob)
 
 
-def branch_stream(device):
-    return None
-
-
 def bce_rows(p, y, widths):
     """Per-row sum of binary cross-entropy over the first widths[r] columns (nn.BCELoss clamps log at -100)."""
     cols = torch.arange(p.shape[1], device=p.device).unsqueeze(0)

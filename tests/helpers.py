@@ -1,7 +1,9 @@
 """Shared test helpers: build the product model from a golden fixture; decoded-caption lists for the evaluation metrics' tests; the digests
-of the evaluation plans' device-facing tables."""
+of the evaluation plans' device-facing tables; the recorder of kernel launches and the recorded training steps of the launch-sequence test."""
+import ctypes
 import hashlib
 import json
+import numbers
 import os
 
 import numpy as np
@@ -78,6 +80,61 @@ def eval_plan_digests(golden_dir):
     scores = {k: _sha(getattr(corpus, k)) for k in ("voc_off", "voc_tok", "ref_tok", "tab_key", "tab_idf", "gauss")}
     scores["batches"] = [plan_digest(corpus.plan([dict(key=v["key"], oov_word_dict=v["oov"]) for v in b["videos"]])) for b in g["batches"]]
     return dict(ingredient_f1=ingredient, caption_scores=scores)
+
+
+class LaunchRecorder:
+    """``with LaunchRecorder() as rec:`` — every kernel launch made through ``_lib.call`` inside the block is kept in ``rec.launches`` as
+    [kernel name, [values of its non-pointer arguments]]: the arguments whose type in ``_lib.declarations()`` is not ``c_void_p`` (shapes,
+    strides, flags, table entry counts); addresses and the stream are dropped, so two runs of the same code give the same record."""
+
+    def __enter__(self):
+        from svpc_amd import _lib
+        decls, keep, inner = _lib.declarations(), {}, _lib.call
+        self.launches = []
+        self._lib, self._inner = _lib, inner
+
+        def call(name, *args):
+            k = keep.get(name)
+            if k is None:
+                k = keep[name] = [i for i, t in enumerate(decls["svpc_" + name][1]) if t is not ctypes.c_void_p]
+            self.launches.append([name, [a if a is None else int(a) if isinstance(a, numbers.Integral) else float(a)
+                                         for a in (args[i] for i in k)]])
+            return inner(name, *args)
+        _lib.call = call
+        return self
+
+    def __exit__(self, *exc):
+        self._lib.call = self._inner
+        return False
+
+
+TRAIN_LAUNCH_CASES = [("tiny", "fp32"), ("c1", "bf16"), ("c1", "bf16x3")]      # (fixture, precision), model type vivt
+
+
+def train_launches(case, precision, golden_dir, device="cuda:0", steps=2):
+    """The launches of ``steps`` consecutive eager training steps on a golden fixture (forward, backward, ``join_side``, fused optimizer
+    step; gradients written straight into the optimizer's arena, which one unrecorded backward builds first) → one
+    ``LaunchRecorder.launches`` list per step.  tests/golden/train_launches.json records them (tools/make_golden_train_launches.py)."""
+    from svpc_amd import ops
+    from svpc_amd.optim import FusedBertAdam
+    ops.set_precision(precision)
+    try:
+        _, _, batch, model = build_model(case, "vivt", golden_dir, device)
+        fargs = syn.forward_args(batch)
+        opt = FusedBertAdam(list(model.named_parameters()))
+        opt.zero_grad(); model(*fargs)[0].backward(); opt.ensure_built()
+        out = []
+        for _ in range(steps):
+            with LaunchRecorder() as rec:
+                opt.zero_grad()
+                model(*fargs)[0].backward()
+                ops.join_side()
+                opt.step()
+            out.append(rec.launches)
+        torch.cuda.synchronize()
+        return out
+    finally:
+        ops.set_precision("fp32")
 
 
 def product_sources_sha16():
