@@ -532,6 +532,29 @@ int svpc_beam_step_groups(const float* scores, int ld, const int* row_c, const i
                           int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
                           int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, int groups, const float* pen, float* aug,
                           svpc_stream_t stream);
+/* lexically constrained beam search (Post & Vilar 2018, dynamic beam allocation; fairseq's unordered --constraints): svpc_beam_step_ctl
+ * whose sentences each have up to 4 phrases of 1 … 4 extended ids that a caption must contain.  cons: (n_sent, 4, 4) int32, a phrase the
+ * leading non-negative ids of its row (the rest −1), a sentence's constraints its leading non-empty rows.  cstate ((T·beam,) int32, in
+ * place, start 0): bits 0–3 one bit per constraint met, bits 4–6 cur + 1 (0: no phrase in progress), bits 8–10 off, the ids of phrase cur
+ * matched so far.  A picked word c of an unfinished parent: cur >= 0 and c == phrase[cur][off] → off += 1 (a complete phrase sets its bit
+ * and clears cur, off); otherwise the progress is dropped and the lowest unmet phrase starting with c starts (length 1: is met).  A
+ * finished parent keeps its state, a fill row gets 0; bank n = Σ len of the met phrases + off.  (Not a string matcher: phrase `a a b` is
+ * not completed by the text `a a a b`.)  Candidates of an unfinished row: the allowed columns of svpc_beam_step_ctl, eos also skipped
+ * while a constraint is unmet; of these its top-beam by (raw, column) and its forced columns (phrase[cur][off], or without progress the
+ * first ids of all unmet phrases) whose child has cum' > −inf.  Live candidates (cum' finite) rank inside their bank by
+ * svpc_beam_step_ctl's order; the rows are filled in ascending (rank in bank, −bank), dead candidates last in svpc_beam_step_ctl's
+ * order.  cum stays the model's sum; len is required.  With no constraints it is svpc_beam_step_ctl bit for bit. */
+int svpc_beam_step_cons(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                        int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in, const int* rows_in,
+                        int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int min_len,
+                        int ngram, const unsigned* excl, int excl_v, const double* lp, int* len, const int* cons, int* cstate,
+                        svpc_stream_t stream);
+/* end of the constrained beam decode: svpc_beam_finalize_nbest in the order: rows with cum = −inf last (by beam index); above them more
+ * constraints met (bits 0–3 of cstate) first, then the higher (double)cum / lp[len], then the lower beam index.  best_met ((n_sent,
+ * n_best)): the rows' met masks. */
+int svpc_beam_finalize_cons(const float* cum, const int* len, const double* lp, const int* ext, const int* cstate, int ld_tok, int n_sent,
+                            int beam, int lt, int n_best, int* best_ids, float* best_score, int* best_len, int* best_met,
+                            svpc_stream_t stream);
 /* end of the beam decode, n-best: per sentence its n_best (1 … beam) hypotheses in order of (double)cum / lp[len] (lp NULL: cum), ties to
  * the lower beam index; their first lt ids of `ext` into best_ids ((n_sent, n_best, lt)), cum into best_score and len into best_len
  * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */

@@ -2446,6 +2446,123 @@ def beam_step_groups(scores, row_c, row_x, beam, groups, pos, logits, unk, eos, 
     return parent, nxt_ext, nxt
 
 
+CONS_MAX = 4                    # constraints (phrases) of a sentence
+CONS_LEN = 4                    # extended ids of a phrase
+
+
+def check_constraints(constraints, batch_step_num, c_list, lt):
+    """The lexical constraints of a constrained beam decode, checked on the host (ValueError) → the (T, CONS_MAX, CONS_LEN) int32 host
+    table ``beam_step_cons`` reads (a phrase: the leading ids of its row, the rest −1; a sentence's phrases: its leading rows).
+    ``constraints``: per video a list of S_b (``batch_step_num``) entries, each None / empty (no constraint) or a list of at most CONS_MAX
+    phrases of 1 … CONS_LEN extended ids; an id is a word of the video's C_b = ``c_list[b]`` columns other than PAD, BOS, EOS and UNK;
+    the ids of a sentence's phrases together must leave room for BOS and EOS: Σ len ≤ ``lt`` − 2."""
+    from .synthetic import BOS, EOS, PAD, UNK
+    steps = [int(s) for s in batch_step_num]
+    if isinstance(constraints, (str, bytes)) or not hasattr(constraints, "__len__") or len(constraints) != len(steps) or len(c_list) != len(steps):
+        raise ValueError("constraints must hold one list per video (%d videos)" % len(steps))
+    rows = [-1] * (sum(steps) * CONS_MAX * CONS_LEN)           # (filled as a flat Python list: one tensor construction per call)
+    t = 0
+    for b, (per_video, S_b) in enumerate(zip(constraints, steps)):
+        if isinstance(per_video, (str, bytes)) or not hasattr(per_video, "__len__") or len(per_video) != S_b:
+            raise ValueError("constraints of video %d must hold one entry per sentence (%d sentences)" % (b, S_b))
+        for s, phrases in enumerate(per_video):
+            phrases = [] if phrases is None else phrases
+            if isinstance(phrases, (str, bytes)) or not hasattr(phrases, "__len__"):
+                raise ValueError("constraints of video %d sentence %d must be a list of phrases, got %r" % (b, s, phrases))
+            if len(phrases) > CONS_MAX:
+                raise ValueError("video %d sentence %d has %d phrases, at most %d are supported" % (b, s, len(phrases), CONS_MAX))
+            total = 0
+            for j, phrase in enumerate(phrases):
+                if isinstance(phrase, (str, bytes)) or not hasattr(phrase, "__len__"):
+                    raise ValueError("a phrase must be a list of ids, got %r (video %d sentence %d)" % (phrase, b, s))
+                if not 1 <= len(phrase) <= CONS_LEN:
+                    raise ValueError("a phrase holds 1..%d ids, got %d (video %d sentence %d)" % (CONS_LEN, len(phrase), b, s))
+                for q, w in enumerate(phrase):
+                    w = _as_int("a constraint id", w.item() if isinstance(w, torch.Tensor) and w.dim() == 0 else w)
+                    if w in (PAD, BOS, EOS, UNK):
+                        raise ValueError("a constraint id may not be PAD, BOS, EOS or UNK, got %d (video %d sentence %d)" % (w, b, s))
+                    if not 0 <= w < int(c_list[b]):
+                        raise ValueError("constraint id %d is outside the %d columns of video %d" % (w, int(c_list[b]), b))
+                    rows[(t * CONS_MAX + j) * CONS_LEN + q] = w
+                total += len(phrase)
+            if total > lt - 2:
+                raise ValueError("the phrases of video %d sentence %d hold %d ids, a caption has room for %d (Lt - 2)" % (b, s, total, lt - 2))
+            t += 1
+    return torch.tensor(rows, dtype=torch.int32).view(sum(steps), CONS_MAX, CONS_LEN)
+
+
+def _check_cons(fn, cons, cstate, T, R, device):
+    if cons.dtype != torch.int32 or tuple(cons.shape) != (T, CONS_MAX, CONS_LEN) or not cons.is_contiguous() or cons.device != device:
+        raise ValueError("%s: cons must be a contiguous int32 (T, %d, %d) table on the scores' device" % (fn, CONS_MAX, CONS_LEN))
+    if not _row_vec(cstate, R, torch.int32, device):
+        raise ValueError("%s: cstate must be contiguous int32 (T·beam,) on the scores' device" % fn)
+
+
+def beam_step_cons(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, cstate, finished, length, toks_in, toks_out, slot_rows, cons,
+                   *, min_length=0, block_ngram_repeat=0, exclusion=None, lp=None):
+    """One selection step of lexically constrained beam search (svpc_beam_step_cons): ``beam_step`` with controls whose sentences have up
+    to CONS_MAX phrases that a caption must contain — ``cons`` the (T, CONS_MAX, CONS_LEN) int32 device table of ``check_constraints``,
+    ``cstate`` (T·beam,) int32 the rows' tracker states (start 0).  In place: ``cum``, ``cstate``, ``finished``, ``length`` (required).
+    → (parent, next_ext, next_model) int32 (T·beam,)."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("beam_step_cons: beam width must be 1..%d" % BEAM_MAX)
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("beam_step_cons: scores must be fp32 (T·beam, C) rows with unit column stride")
+    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
+        raise ValueError("beam_step_cons: cum fp32 and finished int32, both contiguous (T·beam,)")
+    _check_cons("beam_step_cons", cons, cstate, R // beam, R, scores.device)
+    lt = toks_in[0].shape[1]
+    for m in tuple(toks_in) + tuple(toks_out):
+        if not _id_rows(m, R, lt, scores.device):
+            raise ValueError("beam_step_cons: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
+    if not 0 <= pos < lt - 1 or slot_rows < lt:
+        raise ValueError("beam_step_cons: position %d outside the %d-column tables" % (pos, lt))
+    if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
+        raise ValueError("beam_step_cons: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
+    if block_ngram_repeat and lt > 64:
+        raise ValueError("beam_step_cons: block_ngram_repeat needs Lt <= 64")
+    if length is None or not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("beam_step_cons: length must be contiguous int32 (T·beam,) on the scores' device")
+    if lp is not None and not _lp_table(lp, lt, scores.device):
+        raise ValueError("beam_step_cons: lp must be a contiguous float64 table of >= Lt entries on the scores' device")
+    bits, vocab = exclusion if exclusion is not None else (None, 0)
+    if exclusion is not None and (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1
+                                  or not bits.is_contiguous() or bits.device != scores.device):
+        raise ValueError("beam_step_cons: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
+    _need_gpu(scores)
+    dev = scores.device
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("beam_step_cons", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
+              int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
+              _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
+              int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _p(cons), _p(cstate), _stream())
+    return parent, nxt_ext, nxt
+
+
+def beam_finalize_cons(cum, ext, beam, n_best, cstate, length=None, lp=None):
+    """→ (ids (T, n_best, Lt) int32, score (T, n_best) fp32, len (T, n_best) int32, met (T, n_best) int32): ``beam_finalize_nbest`` in the
+    order of constrained beam search — rows with cum = −inf last; above them more constraints met (bits 0–3 of ``cstate``) first, then the
+    higher (double)cum / lp[len], then the lower beam index — svpc_beam_finalize_cons."""
+    T, lt = _check_finalize(cum, ext, beam, n_best)
+    if length is not None and not _row_vec(length, T * beam, torch.int32):
+        raise ValueError("beam_finalize_cons: length must be contiguous int32 (T·beam,)")
+    if lp is not None and (length is None or not _lp_table(lp, lt)):
+        raise ValueError("beam_finalize_cons: lp must be a contiguous float64 table of >= Lt entries, with length")
+    if not _row_vec(cstate, T * beam, torch.int32, ext.device):
+        raise ValueError("beam_finalize_cons: cstate must be contiguous int32 (T·beam,) on the ids' device")
+    _need_gpu(ext)
+    ids = torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device)
+    score = torch.empty(T, n_best, dtype=torch.float32, device=ext.device)
+    ln = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
+    met = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
+    _lib.call("beam_finalize_cons", _p(cum), _p(length), _p(lp), _p(ext), _p(cstate), lt, T, int(beam), lt, int(n_best), _p(ids), _p(score),
+              _p(ln), _p(met), _stream())
+    return ids, score, ln, met
+
+
 def _check_finalize(cum, ext, beam, n_best=1):
     """the arguments the two final picks share → (T, Lt)"""
     if not 1 <= beam <= BEAM_MAX:

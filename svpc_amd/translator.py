@@ -135,6 +135,28 @@ Restated by tests/diverse_beam_reference.py:
 - ``translate_batch_consensus(source="diverse", num_candidates=K, num_groups=G, diversity_strength=λ)`` decodes K / G rows per group
   (``beam_size`` defaults to K) and picks among them.
 
+**Lexically constrained beam search** (Post & Vilar 2018, "dynamic beam allocation", arXiv 1804.06609; fairseq's unordered
+``--constraints``): ``translate_batch_constrained(model_inputs, constraints, beam_size, n_best)`` →
+``(dec_seq_list, oov_word_dict, score_list, length_list, met_list)``.  Restated by tests/constrained_beam_reference.py:
+
+- a sentence has M ≤ 4 constraints, each a phrase of 1 … 4 extended ids (``constraint_ids`` builds them from words), unordered,
+  duplicates met separately; every hypothesis row carries a tracker state — the constraints met, the phrase in progress and the ids of
+  it matched so far — whose token count n = Σ len of the met phrases + the progress is the row's bank;
+- the tracker: a picked word that continues the phrase in progress advances it (a complete phrase is met); any other word drops the
+  progress and starts the lowest unmet phrase that begins with it.  It is not a string matcher: with the phrase ``a a b`` the text
+  ``a a a b`` does not complete it;
+- candidates of an unfinished row: the allowed columns of the controlled beam step — EOS also barred while a constraint is unmet —, of
+  these the row's top-W by (raw, column) and its forced columns (the next id of the phrase in progress, else the first ids of all unmet
+  phrases) whose child has a finite score; live candidates rank inside their bank by the beam step's order and the W rows are filled
+  best-of-every-bank first, from the highest bank down (fairseq's stride over banks), dead candidates last;
+- ``cum`` stays the model's summed step score (``score_captions`` reproduces it); at the end the rows are ordered by more constraints
+  met, then the final key (double)cum / lp[len], then the lower index, rows with cum = −inf last; ``met_list`` holds the rows' masks;
+- with no constraints it is ``translate_batch_nbest(W, W)`` bit for bit; when Σ len ≤ Lt − 2, no control bans the phrase words and
+  their probabilities are positive, row 0 of the sentence holds every phrase, for every W ≥ 1;
+- the controls that work: ``min_length``, ``length_penalty_*``, ``block_ngram_repeat`` / ``exclusion_tokens`` in sentence scope
+  (``block_ngram_scope="paragraph"``: ValueError); the constraint table is a per-call captured input, so one plan and one graph serve
+  every constraint set of a batch structure and setting.
+
 **Forced scoring** (the GOLD score / gold perplexity of the reference decoder's OpenNMT lineage):
 ``Translator.score_captions(model_inputs, dec_seq_list, unk="bar")`` scores GIVEN captions under decoding conditions (text half masked,
 ``log p`` of the mixed pointer-generator distribution).  The definition, restated by tests/forced_score_reference.py:
@@ -193,12 +215,19 @@ class Decode(object):
     plan cache key.  Outside it: ``n_best`` — the rows per sentence the call returns (0: the chosen caption alone; it only slices the
     result) — and ``seed``, this call's seed (a captured input).  FORCE (``score_captions``): ``width`` is the K given captions per
     sentence, ``sampling`` holds (unk rule, id dtype) — part of the key — and ``given`` this call's (T, K, Lt) ids (a captured input).
-    Diverse beam search: BEAM with ``groups`` = (G, fp32 λ) — part of the key; ``n_best`` is then the rows returned per group."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups")
+    Diverse beam search: BEAM with ``groups`` = (G, fp32 λ) — part of the key; ``n_best`` is then the rows returned per group.
+    Constrained beam search: BEAM with ``cons``, this call's (T, CONS_MAX, CONS_LEN) int32 host table of ``ops.check_constraints`` (a
+    captured input, like ``given``); only the fact that the decode is constrained is part of the key."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons")
 
-    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None):
-        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups = (
-            kind, width, controls, ctl_key, n_best, sampling, seed, given, groups)
+    def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None,
+                 cons=None):
+        self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups, self.cons = (
+            kind, width, controls, ctl_key, n_best, sampling, seed, given, groups, cons)
+
+    @property
+    def constrained(self):
+        return self.cons is not None
 
     @property
     def ranked(self):
@@ -207,7 +236,8 @@ class Decode(object):
 
     @property
     def key(self):
-        return (self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
+        return ((self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
+                + (("constrained",) if self.constrained else ()))
 
 
 class DecodePlan(object):
@@ -220,6 +250,7 @@ class DecodePlan(object):
                  "controls",                                    # ranked: ops.beam_step's keywords (device tables)
                  "rounds", "rows_max",                          # paragraph scope: the round tables, the largest round's rows
                  "groups", "pen",                               # diverse beam search: G, the device penalty table (ops.diversity_table)
+                 "cons",                                        # constrained beam search: the (T, 4, 4) device table, a captured input
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
@@ -412,6 +443,44 @@ class Translator(object):
             return self.translate_batch_nbest(model_inputs, W, nb, **controls)     # (G = 1 is the n-best decode by definition)
         self._beam_width(W, beam_size)
         return self._translate(model_inputs, self.model, decode=Decode(BEAM, W, controls=ctl, ctl_key=key, n_best=nb, groups=(G, lam)))
+
+    @torch.no_grad()
+    def translate_batch_constrained(self, model_inputs, constraints, beam_size=None, n_best=None, **controls):
+        """Lexically constrained beam search (module docstring): a width-``beam_size`` beam search whose captions must
+        contain given phrases.  ``constraints``: per video a list of S_b entries, each None / [] (no constraint) or a list of at most
+        ``ops.CONS_MAX`` phrases of 1 … ``ops.CONS_LEN`` extended ids (``constraint_ids`` builds them from words) →
+        (dec_seq_list, oov_word_dict, score_list, length_list, met_list): per video ids (S_b, K, Lt) int64, cum (S_b, K) fp32, len
+        (S_b, K) int64 and met (S_b, K) int64 — bit j set when phrase j is in the row —, K = ``n_best`` (default ``beam_size``, default
+        ``opt.beam_size``), rows with more constraints met first, then by the final key.  Controls: ``min_length``,
+        ``length_penalty_*`` and ``block_ngram_repeat`` / ``exclusion_tokens`` in sentence scope (``block_ngram_scope="paragraph"``:
+        ValueError).  ValueError on the host for the sizes, the controls and the constraints (``ops.check_constraints``)."""
+        B = self._beam_width(beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2), beam_size)
+        ctl, key = self._controls(controls, beam=B, n_best=n_best if n_best is not None else B)
+        if ctl["block_ngram_scope"] == "paragraph":
+            raise ValueError("block_ngram_scope='paragraph' is not supported with constraints")
+        V = self.model_config.vocab_size
+        c_list = [V + (len(d) if self.model_config.model_mode != "video" else 0) for d in model_inputs[8]]
+        table = ops.check_constraints(constraints, model_inputs[11], c_list, self.model_config.max_t_len)
+        return self._translate(model_inputs, self.model, decode=Decode(BEAM, B, controls=ctl, ctl_key=key, n_best=ctl["n_best"], cons=table))
+
+    @staticmethod
+    def constraint_ids(phrases, word2idx, oov_words):
+        """The phrases of one sentence as extended ids for ``translate_batch_constrained``: ``phrases`` a list of phrases, each a list
+        of words (or one string of blank-separated words); a word of ``oov_words`` — the video's ``oov_word_dict``, word → copied id —
+        takes its copied id, otherwise its id in ``word2idx``; a word in neither could never be generated: ValueError."""
+        out = []
+        for phrase in phrases or []:
+            words = phrase.split() if isinstance(phrase, str) else list(phrase)
+            ids = []
+            for w in words:
+                if oov_words and w in oov_words:
+                    ids.append(int(oov_words[w]))
+                elif w in word2idx:
+                    ids.append(int(word2idx[w]))
+                else:
+                    raise ValueError("the word %r is neither in the vocabulary nor among the video's copied words: it cannot be generated" % (w,))
+            out.append(ids)
+        return out
 
     SAMPLING = dict(random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0)
 
@@ -608,6 +677,8 @@ class Translator(object):
         if decode.groups is not None:          # (like lp: the table lives as long as the plan and its captured graphs)
             dp.groups = decode.groups[0]
             dp.pen = torch.tensor(ops.diversity_table(decode.groups[1], W), dtype=torch.float32, device=dev)
+        if decode.constrained:                 # the call's constraint table is copied into this buffer before the eager run or the replay
+            dp.cons = torch.empty(T, ops.CONS_MAX, ops.CONS_LEN, dtype=torch.int32, device=dev)
         if decode.kind == SAMPLE:
             # every sample's ancestry is itself, so the KV-cache rows of row r are r·Lt + j (one static table); the seed source (fixed,
             # value) and the seed the decode used are captured device words
@@ -828,7 +899,9 @@ class Translator(object):
         extended ids, KV-cache ancestry) pairs — children are written from their parents' rows — start with BOS and the row's own slot at
         position 0, cum with beam 0 alone.  ``history``: ``ops.beam_step``'s, of a paragraph round.  Diverse beam search (``dp.groups``):
         cum and the selection score aug start with row 0 of every group alone, the step is ``ops.beam_step_groups``, and the final
-        order is taken per group (the n-best final pick over n_sent·G "sentences" of Bg rows) → the B rows group-major."""
+        order is taken per group (the n-best final pick over n_sent·G "sentences" of Bg rows) → the B rows group-major.  Constrained
+        beam search (``dp.cons``): every row carries a tracker state (start 0), the step is ``ops.beam_step_cons`` and the final pick
+        ``ops.beam_finalize_cons`` → (ids, cum, len, met)."""
         cfg = side.model.config
         B, Lt, dev = dp.width, cfg.max_t_len, side.wide[0].device
         TB = n_sent * B
@@ -845,6 +918,7 @@ class Translator(object):
             cum[:, :, 1:] = float("-inf")                                      # … row 0 of every group alone
         cum = cum.view(TB)
         aug = cum.clone() if G is not None else None
+        cstate = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.cons is not None else None
         fin = torch.zeros(TB, dtype=torch.int32, device=dev)
         nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
         length = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.ranked else None       # ranked: lengths tracked
@@ -852,13 +926,18 @@ class Translator(object):
         for i in range(Lt - 1):
             t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
             scores = side.scores(rows, ptr, nxt, i, caches, seq_self[i], seq_cross, t_in[2], B)
-            if G is None:
+            if cstate is not None:
+                _, _, nxt = ops.beam_step_cons(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, cstate, fin,
+                                               length, t_in, t_out, Lt, dp.cons, **dp.controls)
+            elif G is None:
                 _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
                                           **ctl)
             else:
                 _, _, nxt = ops.beam_step_groups(scores, ptr["row_c"], row_x, B, G, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, aug, fin,
                                                  length, t_in, t_out, Lt, dp.pen, **dp.controls)
         ext = toks[(Lt - 1) % 2][1]
+        if cstate is not None:   # all B hypotheses: more constraints met first, then the final key
+            return ops.beam_finalize_cons(cum, ext, B, B, cstate, length, dp.controls["lp"])
         if G is not None:    # every group's rows in final-key order
             ids, score, ln = ops.beam_finalize_nbest(cum, ext, B // G, B // G, length, dp.controls["lp"])
             return ids.view(n_sent, B, Lt), score.view(n_sent, B), ln.view(n_sent, B)
@@ -960,6 +1039,8 @@ class Translator(object):
                 dp.seed_src.copy_(torch.tensor([0, 0] if decode.seed is None else [1, decode.seed], dtype=torch.int64))
             if dp.given is not None:          # the captions to score: a captured input too
                 dp.given.copy_(decode.given.view(dp.given.shape))
+            if dp.cons is not None:           # the constraint table: one host-to-device copy per call
+                dp.cons.copy_(decode.cons)
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
             if not self.graph or dev.type != "cuda":
                 out = self._decode_core(model, dp, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
@@ -996,8 +1077,10 @@ class Translator(object):
         # every strategy's result: ids (T, K, Lt), cum (T, K) or None, len (T, K) or None.  The call returns the first n_best of the K rows
         # per sentence, or (n_best 0) the chosen caption alone, without lengths
         k = decode.n_best
-        res, scores, lens = [], [], []
-        for plan, (ids, cum, length) in plans_outs:
+        res, scores, lens, mets = [], [], [], []
+        for plan, out in plans_outs:
+            ids, cum, length = out[:3]
+            met = out[3][:, :k].to(torch.int64) if decode.constrained else None
             if k and decode.groups is not None and k < decode.width // decode.groups[0]:      # the first k rows of every group
                 G, Bg = decode.groups[0], decode.width // decode.groups[0]
                 ids, cum, length = (v.reshape(v.shape[0], G, Bg, *v.shape[2:])[:, :, :k].reshape(v.shape[0], G * k, *v.shape[2:])
@@ -1012,9 +1095,11 @@ class Translator(object):
             ids = ids.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
                 o, n_ = plan.h_step_off[b], plan.h_step_len[b]
-                for lst, t in ((res, ids), (scores, cum), (lens, length)):
+                for lst, t in ((res, ids), (scores, cum), (lens, length), (mets, met)):
                     if t is not None:
                         lst.append(t[o:o + n_])
+        if decode.constrained:
+            return res, oov_word_dict, scores, lens, mets
         return (res, oov_word_dict, scores, lens) if scores else (res, oov_word_dict)
 
     def _decode_graphed(self, model, dp, src, shape, stream=None):
