@@ -560,6 +560,24 @@ int svpc_beam_finalize_cons(const float* cum, const int* len, const double* lp, 
  * ((n_sent, n_best); best_len may be NULL, len may be NULL without lp).  n_best = 1 without lp is svpc_beam_finalize. */
 int svpc_beam_finalize_nbest(const float* cum, const int* len, const double* lp, const int* ext, int ld_tok, int n_sent, int beam, int lt,
                              int n_best, int* best_ids, float* best_score, int* best_len, svpc_stream_t stream);
+/* stochastic beam search (Kool, van Hoof and Welling 2019, arXiv 1903.06059): svpc_beam_step's launch shape, tables and step score over
+ * `beam` rows per sentence, selecting by Gumbel-perturbed log-probabilities, so that a sentence's rows are a sample without replacement
+ * from the model's sequence distribution, in the order drawn.  In place, (n_sent·beam,): cum (fp32, the model's sum, as svpc_beam_step's),
+ * phi (fp64, the log-probability of the row's sequence under the tempered, renormalised model), gkey (fp64, the perturbed log-probability
+ * G), finished, len; a dead row is finished with G = −inf; start: row 0 of a sentence (0, 0, 0, live), the others dead.  A live row h
+ * (global row r): candidates are the columns c < row_c[r] <= max_c <= 4096, c != unk, with a finite step score s_c, eos excluded while
+ * pos + 1 <= min_len; z_c = (double)s_c / temp, L their log-sum-exp, phi_c = phi_h + (z_c − L), g_c = phi_c − log(−log u), u =
+ * (svpc_hash32(*seed, pos, r·4096 + c) + 0.5)·2^-32; the row's first `beam` candidates by higher g, then lower c, are short-listed, Z the
+ * first one's g, and get G'_c = G_h − max(v, 0) − log1p(exp(−|v|)), v = G_h − g_c + log1p(−exp(g_c − Z)).  A finished row with finite G
+ * offers itself (pad, step 0, G' = g = G_h, flat index h·4096 + pad), a dead row and a live row without candidates nothing.  The new rows
+ * 0 … beam − 1 are the sentence's first candidates by higher G', then higher g, then lower flat index h·4096 + c: cum = fp32(cum_h + s_c),
+ * phi = phi_c, G = G'_c, len = pos + 1, finished on eos; leftover slots are dead rows (pad, cum = phi = G = −inf, finished, len = pos + 1,
+ * parent their own slot).  Out as svpc_beam_step's.  *seed is read on the device: graph-capture safe. */
+int svpc_beam_step_gumbel(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits, int unk,
+                          int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in, const int* ext_in,
+                          const int* rows_in, int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext,
+                          int* next_model, double temp, int min_len, const long long* seed, double* phi, double* gkey, int* len, int max_c,
+                          svpc_stream_t stream);
 /* random-sampling decoding step (the random-sampling strategy of the reference's OpenNMT decode-strategy lineage: random_sampling_temp,
  * random_sampling_topk, random_sampling_topp): one wave per sample row r of `scores` (n_rows rows; row r: its first row_c[r] <= max_c <= 4096
  * columns, the last row_x[r] of them copied OOV words).  Step scores as svpc_beam_step's (logits == 0: log p; logits != 0: logit − the

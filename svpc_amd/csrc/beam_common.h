@@ -23,6 +23,21 @@ __device__ __forceinline__ void topb_insert(float (&val)[B], int (&idx)[B], floa
     }
 }
 
+// the same list with an fp64 key (beam_gumbel.hip: the perturbed log-probability g of a column): higher key, then lower column
+__device__ __forceinline__ bool key_better(double v, int c, double w, int d) { return v > w || (v == w && c < d); }
+
+template <int B>
+__device__ __forceinline__ void topb_insert_key(double (&val)[B], int (&idx)[B], double v, int c) {
+    if (!key_better(v, c, val[B - 1], idx[B - 1])) return;
+#pragma unroll
+    for (int k = 0; k < B; ++k) {
+        if (key_better(v, c, val[k], idx[k])) {
+            const double tv = val[k]; const int ti = idx[k];
+            val[k] = v; idx[k] = c; v = tv; c = ti;
+        }
+    }
+}
+
 struct BeamArgs {
     const float* scores; int ld; const int* row_c; const int* row_x;
     int pos; int logits; int unk; int eos; int pad; int slot_rows;

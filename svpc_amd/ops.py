@@ -2446,6 +2446,77 @@ def beam_step_groups(scores, row_c, row_x, beam, groups, pos, logits, unk, eos, 
     return parent, nxt_ext, nxt
 
 
+def check_stochastic_beam(max_t_len, beam_size, seed=None, max_cols=None, random_sampling_temp=1.0, min_length=0):
+    """The settings of a stochastic beam search (Kool et al. 2019) over Lt = ``max_t_len`` positions, checked on the host (ValueError)
+    and normalised → dict(beam_size W (1 … BEAM_MAX), random_sampling_temp τ (finite > 0), min_length m (0 … Lt − 1), seed (None or an
+    int in [0, 2⁶³))).  ``max_cols``: the widest score row C_r = V + X of the batch (≤ SAMPLE_COLS_MAX: the draw index is r·4096 + c)."""
+    W = _as_int("beam_size", beam_size)
+    if not 1 <= W <= BEAM_MAX:
+        raise ValueError("beam_size must be 1..%d, got %d" % (BEAM_MAX, W))
+    if isinstance(random_sampling_temp, bool) or not isinstance(random_sampling_temp, numbers.Real):
+        raise ValueError("random_sampling_temp must be a number, got %r" % (random_sampling_temp,))
+    temp = float(random_sampling_temp)
+    if not math.isfinite(temp) or temp <= 0:
+        raise ValueError("random_sampling_temp must be finite and > 0, got %r" % (random_sampling_temp,))
+    m = _as_int("min_length", min_length)
+    if not 0 <= m <= max_t_len - 1:
+        raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (max_t_len - 1, m))
+    if seed is not None:
+        seed = _as_int("seed", seed)
+        if not 0 <= seed < 1 << 63:
+            raise ValueError("seed must be None or an integer in [0, 2**63), got %d" % seed)
+    if max_cols is not None and int(max_cols) > SAMPLE_COLS_MAX:
+        raise ValueError("stochastic beam search reads score rows of at most %d columns (vocabulary + copied words), got %d"
+                         % (SAMPLE_COLS_MAX, max_cols))
+    return dict(beam_size=W, random_sampling_temp=temp, min_length=m, seed=seed)
+
+
+def stochastic_beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, phi, gkey, finished, length, toks_in, toks_out,
+                         slot_rows, seed, *, temp=1.0, min_length=0, max_cols=None):
+    """One selection step of stochastic beam search (svpc_beam_step_gumbel): ``beam_step``'s tables over ``beam`` rows per sentence,
+    selected by Gumbel-perturbed log-probabilities — the sentence's rows are a sample without replacement, in the order drawn.  In place,
+    all contiguous (T·beam,) on the scores' device: ``cum`` fp32 (the model's score), ``phi`` / ``gkey`` float64 (the tempered
+    log-probability and the perturbed log-probability G of a row; a dead row holds −inf and is finished), ``finished`` / ``length`` int32.
+    ``seed`` is a device int64 (1,) tensor (read by the kernel: a captured graph replays with whatever it holds); ``temp`` τ divides the
+    step scores, EOS is barred while pos + 1 ≤ ``min_length``; ``max_cols``: max(row_c) when the caller knows it (else taken from the
+    host copy).  → (parent, next_ext, next_model) int32 (T·beam,)."""
+    if isinstance(beam, bool) or not isinstance(beam, numbers.Integral) or not 1 <= beam <= BEAM_MAX:
+        raise ValueError("stochastic_beam_step: beam width must be 1..%d" % BEAM_MAX)
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("stochastic_beam_step: scores must be fp32 (T·beam, C) rows with unit column stride")
+    for t, dt in ((cum, torch.float32), (phi, torch.float64), (gkey, torch.float64), (finished, torch.int32), (length, torch.int32)):
+        if not _row_vec(t, R, dt, scores.device):
+            raise ValueError("stochastic_beam_step: cum fp32, phi and gkey float64, finished and length int32, all contiguous (T·beam,) "
+                             "on the scores' device")
+    lt = toks_in[0].shape[1]
+    for m in tuple(toks_in) + tuple(toks_out):
+        if not _id_rows(m, R, lt, scores.device):
+            raise ValueError("stochastic_beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
+    if any(i.data_ptr() == o.data_ptr() for i, o in zip(toks_in, toks_out)):
+        raise ValueError("stochastic_beam_step: the token and ancestry tables are ping-pong pairs")
+    if not 0 <= pos < lt - 1 or slot_rows < lt:
+        raise ValueError("stochastic_beam_step: position %d outside the %d-column tables" % (pos, lt))
+    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
+        raise ValueError("stochastic_beam_step: seed must be a device int64 tensor")
+    if not (math.isfinite(temp) and temp > 0 and 0 <= int(min_length) < lt):
+        raise ValueError("stochastic_beam_step: temp finite > 0, min_length 0..Lt-1")
+    rc = as_idx(row_c)
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > SAMPLE_COLS_MAX or max_c > scores.shape[1] or max_c < 1:
+        raise ValueError("stochastic_beam_step: rows of 1..%d columns, inside the score matrix" % SAMPLE_COLS_MAX)
+    _need_gpu(scores)
+    dev = scores.device
+    parent = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("beam_step_gumbel", _p(scores), scores.stride(0), _p(rc.dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
+              1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
+              _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt), float(temp),
+              int(min_length), _p(seed), _p(phi), _p(gkey), _p(length), int(max_c), _stream())
+    return parent, nxt_ext, nxt
+
+
 CONS_MAX = 4                    # constraints (phrases) of a sentence
 CONS_LEN = 4                    # extended ids of a phrase
 

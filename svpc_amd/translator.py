@@ -113,7 +113,7 @@ plan, row=0)`` gives every video's Bleu_1…4, ROUGE_L and CIDEr against its ref
 of an n-best or sampling result without references — every candidate is scored against the others as pseudo-references (one of the six
 scores above, CIDEr by default, its idf from the plan's corpus) and the one with the highest expected utility wins, per video
 (``scope="paragraph"``: the same row k for all its sentences) or per sentence; ``translate_batch_consensus(model_inputs, plan,
-source="sample" | "nbest", num_candidates=K)`` is the decode followed by it.  On the device, without host synchronisation.
+source="sample" | "nbest" | "diverse" | "stochastic", num_candidates=K)`` is the decode followed by it.  On the device, without host synchronisation.
 
 **Diverse (group) beam search** (Vijayakumar et al. 2016, arXiv 1610.02424; fairseq's ``--diverse-beam-groups`` / ``-strength``, HF's
 "group beam search"): ``translate_batch_diverse(model_inputs, beam_size, num_groups, diversity_strength, n_best)`` →
@@ -156,6 +156,33 @@ Restated by tests/diverse_beam_reference.py:
 - the controls that work: ``min_length``, ``length_penalty_*``, ``block_ngram_repeat`` / ``exclusion_tokens`` in sentence scope
   (``block_ngram_scope="paragraph"``: ValueError); the constraint table is a per-call captured input, so one plan and one graph serve
   every constraint set of a batch structure and setting.
+
+**Stochastic beam search** (Kool, van Hoof and Welling 2019, "Stochastic Beams and Where to Find Them", arXiv 1903.06059):
+``translate_batch_stochastic(model_inputs, beam_size, seed=None, random_sampling_temp=1.0, min_length=0)`` → ``(dec_seq_list,
+oov_word_dict, score_list, length_list, gumbel_list, logq_list)``: per video ids (S_b, W, Lt) int64, cum (S_b, W) fp32, len (S_b, W)
+int64, G (S_b, W) float64 and phi (S_b, W) float64 — W captions per sentence sampled WITHOUT replacement from the model, in the order
+drawn.  Restated by tests/stochastic_beam_reference.py:
+
+- a sentence has W = ``beam_size`` rows (1 ≤ W ≤ 8), row r = t·W + h; a row carries ``cum`` (fp32, the model's summed step score, as
+  beam's — what ``score_captions`` reproduces), ``phi`` (float64, the log-probability of its sequence under the tempered, renormalised
+  model) and ``G`` (float64, the perturbed log-probability); row 0 starts alive at BOS with cum = phi = G = 0, rows 1 … W − 1 *dead*
+  (−inf, finished);
+- a live row's candidates are sampling's K0 (columns c < C_r, c ≠ UNK, step score s_c > −inf, not EOS while p ≤ ``min_length``); z_c =
+  (double)s_c / τ, L their log-sum-exp, φ_c = phi + (z_c − L), g_c = φ_c − log(−log u_c) with sampling's counter-based u_c =
+  (svpc_hash32(seed, i, r·4096 + c) + 0.5)·2⁻³²; the row's first W candidates by higher g, then lower c, are short-listed, Z their
+  maximum, and each gets G̃_c = G − max(v, 0) − log1p(exp(−|v|)), v = G − g_c + log1p(−exp(g_c − Z)) (the truncated-Gumbel transform:
+  the children's perturbed scores conditioned on their maximum being the parent's; the arg max carries G exactly);
+- a finished row with finite G offers itself (PAD, step score 0, everything kept); a dead row, and a live row with an empty K0, nothing;
+- the sentence's new rows are its first W candidates by higher G̃, then higher g, then lower flat index h·4096 + c: cum = fp32(cum +
+  s_c), phi = φ_c, G = G̃_c, len = p, EOS finishes; a copied word keeps its extended id, the model side sees UNK; leftover slots are dead;
+- rows stay in selection order — descending G, the order in which the captions were drawn; no final re-ranking, no length penalty, no
+  n-gram blocking; the temperature changes what is sampled (phi), not cum;
+- so the finite-G rows of a sentence are pairwise different captions, G never increases from parent to child nor from row j to row
+  j + 1, and W = 1 is ``translate_batch_sample(num_samples=1)`` with the same τ, m and seed (ids, lengths and cum bit for bit);
+- ``seed`` as sampling's (fixed: reproducible eagerly and replayed; None: the device seed word advances; ``last_sample_seed``); ValueError
+  on the host for W, τ, m, the seed and rows wider than 4096 columns; TypeError for any other keyword (``random_sampling_topk`` /
+  ``random_sampling_topp`` included); ``incremental=False`` raises NotImplementedError.  Each setting (W, τ, m) has its own plan and
+  captured graph; ``translate_batch_consensus(source="stochastic", num_candidates=K)`` decodes with W = K.
 
 **Forced scoring** (the GOLD score / gold perplexity of the reference decoder's OpenNMT lineage):
 ``Translator.score_captions(model_inputs, dec_seq_list, unk="bar")`` scores GIVEN captions under decoding conditions (text half masked,
@@ -217,13 +244,15 @@ class Decode(object):
     sentence, ``sampling`` holds (unk rule, id dtype) — part of the key — and ``given`` this call's (T, K, Lt) ids (a captured input).
     Diverse beam search: BEAM with ``groups`` = (G, fp32 λ) — part of the key; ``n_best`` is then the rows returned per group.
     Constrained beam search: BEAM with ``cons``, this call's (T, CONS_MAX, CONS_LEN) int32 host table of ``ops.check_constraints`` (a
-    captured input, like ``given``); only the fact that the decode is constrained is part of the key."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons")
+    captured input, like ``given``); only the fact that the decode is constrained is part of the key.
+    Stochastic beam search: BEAM with ``stochastic`` = (τ, m) — part of the key — and ``seed`` as sampling's."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons", "stochastic")
 
     def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None,
-                 cons=None):
+                 cons=None, stochastic=None):
         self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups, self.cons = (
             kind, width, controls, ctl_key, n_best, sampling, seed, given, groups, cons)
+        self.stochastic = stochastic
 
     @property
     def constrained(self):
@@ -232,12 +261,12 @@ class Decode(object):
     @property
     def ranked(self):
         """decoding controls and / or n-best: lengths tracked, all B final hypotheses sorted by their key"""
-        return self.kind == BEAM and (self.n_best > 0 or self.ctl_key is not None)
+        return self.kind == BEAM and self.stochastic is None and (self.n_best > 0 or self.ctl_key is not None)
 
     @property
     def key(self):
         return ((self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
-                + (("constrained",) if self.constrained else ()))
+                + (("constrained",) if self.constrained else ()) + ((("stochastic",) + tuple(self.stochastic),) if self.stochastic is not None else ()))
 
 
 class DecodePlan(object):
@@ -252,6 +281,7 @@ class DecodePlan(object):
                  "groups", "pen",                               # diverse beam search: G, the device penalty table (ops.diversity_table)
                  "cons",                                        # constrained beam search: the (T, 4, 4) device table, a captured input
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
+                 "stochastic",                                  # stochastic beam search: ops.stochastic_beam_step's keywords (+ the seed words)
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
                  "graphs")                                      # replay stream → (graph, captured inputs, outputs, signature)
@@ -499,6 +529,30 @@ class Translator(object):
         return self._translate(model_inputs, self.model, decode=Decode(SAMPLE, R, n_best=R, seed=s["seed"], sampling=tuple(
             s[k] for k in ("random_sampling_temp", "random_sampling_topk", "random_sampling_topp", "min_length"))))
 
+    STOCHASTIC = dict(random_sampling_temp=1.0, min_length=0)
+
+    @torch.no_grad()
+    def translate_batch_stochastic(self, model_inputs, beam_size=None, seed=None, **kw):
+        """Stochastic beam search of width W = ``beam_size`` (default ``opt.beam_size``; module docstring): W captions
+        per sentence sampled WITHOUT replacement from the model, in the order drawn → (dec_seq_list, oov_word_dict, score_list,
+        length_list, gumbel_list, logq_list): per video ids (S_b, W, Lt) int64, cum (S_b, W) fp32 (the model's summed step scores, what
+        ``score_captions`` reproduces), len (S_b, W) int64, G (S_b, W) float64 (the perturbed log-probabilities, descending) and phi
+        (S_b, W) float64 (the log-probability of the row under the tempered, renormalised model); a sentence with fewer than W captions
+        of positive probability ends with dead rows (PAD, −inf).  Keywords ``random_sampling_temp`` and ``min_length`` override ``opt``
+        attributes of the same name; ``seed`` as ``translate_batch_sample``'s.  ValueError on the host for W, τ, m, the seed and rows wider
+        than 4096 columns; TypeError for any other keyword; ``incremental=False`` raises NotImplementedError."""
+        unknown = set(kw) - set(self.STOCHASTIC)
+        if unknown:
+            raise TypeError("unknown stochastic beam search keyword(s): %s" % ", ".join(sorted(unknown)))
+        val = {k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.STOCHASTIC.items()}
+        s = ops.check_stochastic_beam(self.max_t_len, beam_size if beam_size is not None else getattr(self.opt, "beam_size", 2), seed,
+                                      self._max_cols(model_inputs), **val)
+        if not self.incremental:
+            raise NotImplementedError("stochastic beam search decodes incrementally only (Translator(incremental=True))")
+        W = s["beam_size"]
+        return self._translate(model_inputs, self.model, decode=Decode(BEAM, W, n_best=W, seed=s["seed"],
+                                                                       stochastic=(s["random_sampling_temp"], s["min_length"])))
+
     @staticmethod
     def _clean(dec_seq_list, row, remove_dup=True):
         """→ (words (T, Lt), len (T,)) int32 of the stacked decode, and the videos' row counts"""
@@ -615,7 +669,8 @@ class Translator(object):
                                   weights="uniform", **decode_kw):
         """``translate_batch_sample(num_samples=num_candidates)`` (``source="sample"``), ``translate_batch_nbest(n_best=
         num_candidates)`` (``"nbest"``; ``beam_size`` defaults to ``num_candidates``) or ``translate_batch_diverse(num_groups=G,
-        n_best=num_candidates / G)`` (``"diverse"``; ``beam_size`` defaults to ``num_candidates``) followed by ``consensus`` →
+        n_best=num_candidates / G)`` (``"diverse"``; ``beam_size`` defaults to ``num_candidates``) or
+        ``translate_batch_stochastic(beam_size=num_candidates)`` (``"stochastic"``) followed by ``consensus`` →
         (dec_seq_list, oov_word_dict, pick_list): one (S_b, Lt) int64 caption matrix per video, as greedy returns."""
         ops.check_consensus(num_candidates, utility, scope, weights)
         if source == "sample":
@@ -631,8 +686,10 @@ class Translator(object):
                 raise ValueError("num_candidates must be num_groups times 1..%d rows per group, got %d with %d groups" % (W // G, num_candidates, G))
             dec, oov, sc, ln = self.translate_batch_diverse(model_inputs, W, G, decode_kw.pop("diversity_strength", None), num_candidates // G,
                                                             **decode_kw)
+        elif source == "stochastic":
+            dec, oov, sc, ln = self.translate_batch_stochastic(model_inputs, num_candidates, **decode_kw)[:4]
         else:
-            raise ValueError("source must be \"sample\", \"nbest\" or \"diverse\", got %r" % (source,))
+            raise ValueError("source must be \"sample\", \"nbest\", \"diverse\" or \"stochastic\", got %r" % (source,))
         r = self.consensus(dec, plan, sc, ln, utility, scope, weights)
         return r.dec_seq_list, oov, r.pick_list
 
@@ -686,6 +743,10 @@ class Translator(object):
             dp.sampling = dict(temp=temp, topk=topk, topp=topp, min_length=m, max_cols=dp.ptr_hyp["c_max"])
             dp.key_rows = (torch.arange(T * W, dtype=torch.int32, device=dev).unsqueeze(1) * Lt +
                            torch.arange(Lt, dtype=torch.int32, device=dev)).contiguous()
+            dp.seed_src, dp.seed_used = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+        if decode.stochastic is not None:      # the seed source and the seed the decode used: captured device words, as sampling's
+            temp, m = decode.stochastic
+            dp.stochastic = dict(temp=temp, min_length=m, max_cols=dp.ptr_hyp["c_max"])
             dp.seed_src, dp.seed_used = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
         if len(self._preps) > 32:
             self._preps.clear()
@@ -889,9 +950,13 @@ class Translator(object):
 
     def _beam_iterations(self, dp, side):
         """A beam decode over the T·B hypothesis rows of the whole batch → (ids (T, 1, Lt) int32, score (T, 1) fp32, None); with controls
-        or n-best (``dp.ranked``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order."""
+        or n-best (``dp.ranked``) → (ids (T, B, Lt) int32, cum (T, B) fp32, len (T, B) int32) in final-key order; stochastic beam search
+        → (ids, cum, len, G (T, B) float64, phi (T, B) float64) in the order drawn."""
+        dev = side.wide[0].device
+        if dp.stochastic is not None:          # this decode's seed, on the device, exactly as ``_sample_iterations`` takes it
+            ops.sample_seed(dp.seed_src, self._seed_word_on(dev), dp.seed_used)
         return self._beam_search(dp, side, side.rows(), dp.T, dp.ptr_hyp, dp.x_hyp, side.caches(dp.T * dp.width),
-                                 self._self_segs(dp, side.model.config.max_t_len, side.wide[0].device), side.seq_cross(dp))
+                                 self._self_segs(dp, side.model.config.max_t_len, dev), side.seq_cross(dp))
 
     @staticmethod
     def _beam_search(dp, side, rows, n_sent, ptr, row_x, caches, seq_self, seq_cross, history=None):
@@ -901,7 +966,10 @@ class Translator(object):
         cum and the selection score aug start with row 0 of every group alone, the step is ``ops.beam_step_groups``, and the final
         order is taken per group (the n-best final pick over n_sent·G "sentences" of Bg rows) → the B rows group-major.  Constrained
         beam search (``dp.cons``): every row carries a tracker state (start 0), the step is ``ops.beam_step_cons`` and the final pick
-        ``ops.beam_finalize_cons`` → (ids, cum, len, met)."""
+        ``ops.beam_finalize_cons`` → (ids, cum, len, met).  Stochastic beam search (``dp.stochastic``): every row also carries phi
+        and G (float64; start 0 on row 0, −inf on the dead rows 1 … B − 1, which start finished), the step is
+        ``ops.stochastic_beam_step`` with the seed ``dp.seed_used`` holds, and there is no final pick: the rows are already in the order
+        drawn → (ids, cum, len, G, phi)."""
         cfg = side.model.config
         B, Lt, dev = dp.width, cfg.max_t_len, side.wide[0].device
         TB = n_sent * B
@@ -921,12 +989,20 @@ class Translator(object):
         cstate = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.cons is not None else None
         fin = torch.zeros(TB, dtype=torch.int32, device=dev)
         nxt = torch.full((TB,), BOS, dtype=torch.int32, device=dev)
-        length = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.ranked else None       # ranked: lengths tracked
+        length = torch.zeros(TB, dtype=torch.int32, device=dev) if dp.ranked or dp.stochastic is not None else None   # lengths tracked
+        phi = gk = None
+        if dp.stochastic is not None:
+            phi = cum.to(torch.float64)
+            gk = phi.clone()
+            fin = torch.isinf(cum).to(torch.int32)
         ctl = dict(dp.controls, length=length, history=history) if dp.ranked else {}
         for i in range(Lt - 1):
             t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
             scores = side.scores(rows, ptr, nxt, i, caches, seq_self[i], seq_cross, t_in[2], B)
-            if cstate is not None:
+            if phi is not None:
+                _, _, nxt = ops.stochastic_beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, phi, gk,
+                                                     fin, length, t_in, t_out, Lt, dp.seed_used, **dp.stochastic)
+            elif cstate is not None:
                 _, _, nxt = ops.beam_step_cons(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, cstate, fin,
                                                length, t_in, t_out, Lt, dp.cons, **dp.controls)
             elif G is None:
@@ -936,6 +1012,8 @@ class Translator(object):
                 _, _, nxt = ops.beam_step_groups(scores, ptr["row_c"], row_x, B, G, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, aug, fin,
                                                  length, t_in, t_out, Lt, dp.pen, **dp.controls)
         ext = toks[(Lt - 1) % 2][1]
+        if phi is not None:      # no final re-ranking: selection order is descending G, the order drawn
+            return ext.view(n_sent, B, Lt), cum.view(n_sent, B), length.view(n_sent, B), gk.view(n_sent, B), phi.view(n_sent, B)
         if cstate is not None:   # all B hypotheses: more constraints met first, then the final key
             return ops.beam_finalize_cons(cum, ext, B, B, cstate, length, dp.controls["lp"])
         if G is not None:    # every group's rows in final-key order
@@ -1009,6 +1087,8 @@ class Translator(object):
         dev = video_features_list[0].device
         if decode.kind == SAMPLE and dev.type != "cuda":
             raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
+        if decode.stochastic is not None and dev.type != "cuda":
+            raise ops._lib.SvpcKernelError("stochastic beam search decodes on the GPU only (no CPU fallback exists)")
         if decode.kind == FORCE and dev.type != "cuda":
             raise ops._lib.SvpcKernelError("forced scoring runs on the GPU only (no CPU fallback exists)")
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
@@ -1077,10 +1157,11 @@ class Translator(object):
         # every strategy's result: ids (T, K, Lt), cum (T, K) or None, len (T, K) or None.  The call returns the first n_best of the K rows
         # per sentence, or (n_best 0) the chosen caption alone, without lengths
         k = decode.n_best
-        res, scores, lens, mets = [], [], [], []
+        res, scores, lens, mets, gums, logqs = [], [], [], [], [], []
         for plan, out in plans_outs:
             ids, cum, length = out[:3]
             met = out[3][:, :k].to(torch.int64) if decode.constrained else None
+            gum, logq = (out[3], out[4]) if decode.stochastic is not None else (None, None)
             if k and decode.groups is not None and k < decode.width // decode.groups[0]:      # the first k rows of every group
                 G, Bg = decode.groups[0], decode.width // decode.groups[0]
                 ids, cum, length = (v.reshape(v.shape[0], G, Bg, *v.shape[2:])[:, :, :k].reshape(v.shape[0], G * k, *v.shape[2:])
@@ -1095,11 +1176,13 @@ class Translator(object):
             ids = ids.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
                 o, n_ = plan.h_step_off[b], plan.h_step_len[b]
-                for lst, t in ((res, ids), (scores, cum), (lens, length), (mets, met)):
+                for lst, t in ((res, ids), (scores, cum), (lens, length), (mets, met), (gums, gum), (logqs, logq)):
                     if t is not None:
                         lst.append(t[o:o + n_])
         if decode.constrained:
             return res, oov_word_dict, scores, lens, mets
+        if decode.stochastic is not None:
+            return res, oov_word_dict, scores, lens, gums, logqs
         return (res, oov_word_dict, scores, lens) if scores else (res, oov_word_dict)
 
     def _decode_graphed(self, model, dp, src, shape, stream=None):
