@@ -727,6 +727,31 @@ int svpc_seq_nll_bwd(const float* scores, int ld, const int* row_c, int max_c, c
 int svpc_scst_weights(const double* reward, const double* greedy, const int* row_vid, int n_vid, int k, int n_sent, int rule,
                       double* advantage, float* w, svpc_stream_t stream);
 
+/* ---- unlikelihood training against repetition.  Layout, tgt / len / finished as the sequence log-likelihood above.  neg
+ *      (n_cap, lt − 1, m) int32, 1 <= m <= 64, lists the negative columns of every scored position (−1: none); a listing counts when it is a
+ *      candidate (0 <= c < row_c[r], c != unk) and i < len[r]; a column listed twice counts twice.  term = −log1p(−p_c) when 1 − p_c >= 1e-5,
+ *      else −log 1e-5 with a zero gradient; p_c = the probability, or exp(logit − the log-sum-exp of the row without unk), in fp64. */
+/* One wave per caption row, lt − 1 <= 64.  rule 0 ("token", neg has m = lt − 1): entry (r, i) lists the distinct columns among tgt[r, 1 … i]
+ * in order of first occurrence without tgt[r, i + 1] and non-candidates, −1 after them and on the rows i >= len[r].  rule 1 ("ngram", m = 1,
+ * 1 <= ngram <= 4): the words of row r are tgt[r, 1 … nw], nw = len[r] − finished[r]; a gram of ngram words inside one caption is a repeat
+ * when an equal gram starts earlier in the caption or, with paragraph != 0, anywhere in row s·k + (r mod k) of a sentence s with
+ * sent_first[r / k] <= s < r / k (sent_first (n_cap / k,): the first sentence of each sentence's video); entry (r, p − 1) = tgt[r, p] when
+ * position p lies inside a repeat gram, else −1.  npen (n_cap,) = the counted negatives, nrep (n_cap,) = the repeat grams (0 under rule 0). */
+int svpc_ul_negatives(const int* tgt, const int* len, const int* finished, const int* row_c, int n_cap, int lt, int unk, int rule, int ngram,
+                      int paragraph, const int* sent_first, int k, int* neg, int* npen, int* nrep, svpc_stream_t stream);
+/* step / cum / barred as svpc_seq_nll_fwd (the same bits); ulstep (n_cap, lt − 1) = fp32(sum of the row's terms) (0 past the end), ul
+ * (n_cap,) = fp32(ul + ulstep) in position order, loss (1,) = fp32(−sum row_w·cum + sum row_u·ul) over the captions not barred, products and
+ * sums in fp64 in svpc_seq_nll_fwd's order (row_u all 0: its bits).  Three launches. */
+int svpc_seq_ul_fwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const int* neg, int m,
+                    const float* row_w, const float* row_u, int n_cap, int lt, int logits, int unk, float* step, float* ulstep, float* cum,
+                    float* ul, int* barred, float* loss, svpc_stream_t stream);
+/* dscores as svpc_seq_nll_bwd, every element written, with the unlikelihood term's gradient on the rows that are not zero: probabilities,
+ * dl·row_u[r] / (1 − p_c) added at column c per counted, unclamped listing of c; logits, dl·row_u[r]·(a_c − A·p_c) added at every candidate
+ * column, a_c = the sum of p_c / (1 − p_c) over those listings of c, A = the sum of a_c.  A row with dl·row_u[r] = 0 has svpc_seq_nll_bwd's bits. */
+int svpc_seq_ul_bwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const int* barred,
+                    const int* neg, int m, const float* row_w, const float* row_u, const float* dl, int n_cap, int lt, int logits, int unk,
+                    float* dscores, int ld_out, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

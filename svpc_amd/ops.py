@@ -3362,3 +3362,148 @@ def seq_nll(scores, row_c, tgt, length, row_w, logits, unk_id, max_cols=None):
         raise ValueError("seq_nll: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
     _need_gpu(scores)
     return _SeqNll.apply(_c(scores), rc.dev(scores.device), tgt, length, row_w, 1 if logits else 0, int(unk_id), max_c)
+
+
+# ------------------------------------------------------------------------------------------------ unlikelihood training
+UL_RULES = ("token", "ngram")
+UL_SCOPES = ("caption", "paragraph")
+UL_MAX_NEG = 64                 # negatives per position: one lane each
+UL_EPS = 1e-5                   # the clamp on 1 − p (svpc_seq_ul_fwd): a defined constant
+
+
+def check_unlikelihood(rule="token", ngram=4, scope="caption", alpha=None, lt=None, m=None, neg=None, rows=None, device=None, row_w=None,
+                       row_u=None, weights=None, ul_weights=None, shape=None):
+    """Host checks of unlikelihood training (DESIGN §11.13; ValueError for each): ``rule`` "token" or "ngram"; ``ngram`` n in 1 … 4;
+    ``scope`` "caption" or "paragraph"; ``alpha`` finite and not negative; ``lt`` at most 65 (one lane per scored position); ``m`` in
+    1 … 64; ``neg`` a contiguous int32 (``rows``, ``lt`` − 1, M) table on ``device``; ``row_w`` / ``row_u`` contiguous fp32 (``rows``,) on
+    ``device``; ``weights`` / ``ul_weights`` floating point of ``shape`` (T, K) or (T·K,).  ``SvpcKernelError`` for a tensor that is not on
+    the GPU (no CPU fallback exists).  → (rule index, n, paragraph scope)."""
+    if rule not in UL_RULES:
+        raise ValueError("rule must be one of %s, got %r" % (", ".join(UL_RULES), rule))
+    if isinstance(ngram, bool) or not isinstance(ngram, numbers.Integral) or not 1 <= int(ngram) <= 4:
+        raise ValueError("unlikelihood penalises repeated n-grams of 1..4 words, got ngram = %r" % (ngram,))
+    if scope not in UL_SCOPES:
+        raise ValueError("scope must be one of %s, got %r" % (", ".join(UL_SCOPES), scope))
+    if alpha is not None and (isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not math.isfinite(alpha) or alpha < 0):
+        raise ValueError("alpha must be a finite number >= 0, got %r" % (alpha,))
+    if lt is not None and not 2 <= int(lt) <= UL_MAX_NEG + 1:
+        raise ValueError("unlikelihood takes captions of 2..%d positions (one lane per scored position), got Lt = %d" % (UL_MAX_NEG + 1, lt))
+    if neg is not None:
+        if not torch.is_tensor(neg) or neg.dim() != 3:
+            raise ValueError("neg must be an int32 (R, Lt - 1, M) table")
+        m = neg.shape[2] if m is None else m
+    if m is not None and not 1 <= int(m) <= UL_MAX_NEG:
+        raise ValueError("1..%d negatives per position, got M = %d" % (UL_MAX_NEG, m))
+    if neg is not None and (neg.dtype != torch.int32 or not neg.is_contiguous() or tuple(neg.shape) != (rows, int(lt) - 1, int(m))
+                            or (device is not None and neg.device != device)):
+        raise ValueError("neg must be a contiguous int32 (%s, %s, %s) table on the scores' device, got %s %s"
+                         % (rows, int(lt) - 1, m, tuple(neg.shape), neg.dtype))
+    for name, t in (("row_w", row_w), ("row_u", row_u)):
+        if t is not None and (not torch.is_tensor(t) or not _row_vec(t, rows, torch.float32, device)):
+            raise ValueError("%s must be contiguous fp32 (%s,) on the scores' device" % (name, rows))
+    for name, t in (("weights", weights), ("ul_weights", ul_weights)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_floating_point()
+                              or tuple(t.shape) not in (tuple(shape), (shape[0] * shape[1],))):
+            raise ValueError("%s must be floating point %s or (%d,), got %s"
+                             % (name, tuple(shape), shape[0] * shape[1], tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    for t in (neg, row_w, row_u, weights, ul_weights):
+        if t is not None and not t.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.ops: unlikelihood training runs on the GPU only (no CPU fallback exists)")
+    return UL_RULES.index(rule), int(ngram), scope == "paragraph"
+
+
+def ul_negatives(tgt, length, finished, row_c, unk_id, eos, rule, ngram=4, scope="caption", sent_first=None, K=1):
+    """The negatives of unlikelihood training, built on the device (svpc_ul_negatives, one launch, no read-back): ``tgt``
+    (R, Lt) / ``length`` / ``finished`` (R,) int32 as ``force_inputs`` returns them under the end-of-caption id ``eos``, ``row_c`` the R
+    rows' column counts → (neg (R, Lt − 1, M) int32, npen (R,) int32 the counted negatives, nrep (R,) int32 the repeat grams).
+    ``rule="token"``: M = Lt − 1, the distinct earlier words of the caption without the position's target.  ``rule="ngram"``: M = 1, the
+    word of every position inside a repeated ``ngram``-gram; ``scope="paragraph"`` also counts a gram of row t′·K + k of an earlier
+    sentence t′ of the video — ``sent_first`` (R / K host ints or an Idx) names the first sentence of each sentence's video."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1]):
+        raise ValueError("ul_negatives: tgt must be a contiguous int32 (R, Lt >= 2) matrix")
+    R, lt = tgt.shape
+    ri, n, paragraph = check_unlikelihood(rule, ngram, scope, lt=lt)
+    if not _row_vec(length, R, torch.int32, tgt.device) or not _row_vec(finished, R, torch.int32, tgt.device):
+        raise ValueError("ul_negatives: length and finished must be contiguous int32 (R,) on tgt's device")
+    if not 0 <= int(unk_id) or int(eos) < 0:
+        raise ValueError("ul_negatives: the UNK and EOS ids are columns")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("ul_negatives: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    sf = None
+    if ri == 1 and paragraph:
+        if isinstance(K, bool) or not isinstance(K, numbers.Integral) or K < 1 or R % int(K):
+            raise ValueError("ul_negatives: K = %r captions per sentence must divide the %d caption rows" % (K, R))
+        if sent_first is None:
+            raise ValueError("ul_negatives: scope=\"paragraph\" needs sent_first, the first sentence of every sentence's video")
+        sf = as_idx(sent_first)
+        if len(sf.host) != R // int(K) or any(not 0 <= int(f) <= t for t, f in enumerate(sf.host)):
+            raise ValueError("ul_negatives: sent_first must name, for each of the %d sentences, a sentence at or before it" % (R // int(K)))
+    _need_gpu(tgt)
+    dev = tgt.device
+    M = lt - 1 if ri == 0 else 1
+    neg = torch.empty(R, lt - 1, M, dtype=torch.int32, device=dev)
+    npen = torch.empty(R, dtype=torch.int32, device=dev)
+    nrep = torch.empty(R, dtype=torch.int32, device=dev)
+    _lib.call("ul_negatives", _p(tgt), _p(length), _p(finished), _p(rc.dev(dev)) if R else None, R, lt, int(unk_id), ri, n, 1 if paragraph else 0,
+              _p(sf.dev(dev)) if sf is not None and R else None, int(K) if sf is not None else 1, _p(neg), _p(npen), _p(nrep), _stream())
+    return neg, npen, nrep
+
+
+class _SeqUl(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, neg, row_w, row_u, logits, unk_id, max_c):
+        R, lt = tgt.shape
+        dev = scores.device
+        step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        ulstep = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        cum = torch.empty(R, dtype=torch.float32, device=dev)
+        ul = torch.empty(R, dtype=torch.float32, device=dev)
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_ul_fwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(neg), neg.shape[2], _p(row_w), _p(row_u),
+                  R, lt, logits, unk_id, _p(step), _p(ulstep), _p(cum), _p(ul), _p(barred), _p(loss), _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, neg, row_w, row_u)
+        ctx.cfg = (R, lt, logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred, ul, ulstep)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred, ul, ulstep
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 10
+        scores, rc, tgt, length, barred, neg, row_w, row_u = ctx.saved_tensors
+        R, lt, logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        _lib.call("seq_ul_bwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(neg), neg.shape[2], _p(row_w),
+                  _p(row_u), _p(dl), R, lt, logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return (dscores,) + (None,) * 9
+
+
+def seq_ul(scores, row_c, tgt, length, neg, row_w, row_u, logits, unk_id, max_cols=None):
+    """``seq_nll`` plus the unlikelihood term (svpc_seq_ul_fwd / _bwd), differentiable in ``scores`` only: ``neg``
+    (R, Lt − 1, M) int32 lists each position's negative columns (−1: none; ``ul_negatives`` builds the two rules' tables), ``row_u`` (R,)
+    fp32 the captions' unlikelihood weights, the rest as ``seq_nll`` takes it → (loss () fp32 = −Σ w_r·cum_r + Σ u_r·ul_r over the captions
+    that are not barred, cum, step, barred as ``seq_nll`` returns them — the same bits —, ul (R,) fp32, ulstep (R, Lt − 1) fp32: the sum
+    over a position's counted negatives c of −log(1 − p_c), clamped at 1 − p_c = 1e-5).  With ``row_u`` all zero the loss and its gradient
+    have ``seq_nll``'s bits."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_ul: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_ul: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_ul: length must be contiguous int32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_ul: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_ul: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    check_unlikelihood(lt=lt, neg=neg, rows=R, device=scores.device, row_w=row_w, row_u=row_u)
+    _need_gpu(scores)
+    return _SeqUl.apply(_c(scores), rc.dev(scores.device), tgt, length, neg, row_w, row_u, 1 if logits else 0, int(unk_id), max_c)

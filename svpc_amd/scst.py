@@ -51,28 +51,26 @@ def _force_plan(model, plan, K, dicts, c_list, dev):
     return fp
 
 
-def sequence_loss(translator, model_inputs, dec_seq_list, weights):
-    """The graded forced pass: loss = −Σ_{(t,k) not barred} w[t,k] · cum[t,k], cum the model's log-probability of the given caption
-    (``Translator.score_captions``'s ``cum`` under ``unk="bar"``), differentiable in every parameter the decode-conditions pass touches.
-    ``model_inputs`` as ``translate_batch`` takes them (only the video half is read, so the caller's ids and masks are left as they
-    are); ``dec_seq_list`` per video (S_b, K, Lt) or (S_b, Lt) int64 / int32 extended ids, 1 ≤ K ≤ 16; ``weights`` (T, K) or (T·K,)
-    floating point on the device (rounded to fp32).  ``model.train()``: dropout is on (the model's own RNG, advanced once per call);
-    ``model.eval()``: deterministic.  → a namespace: ``loss`` () fp32 (the only result with a gradient), ``cum`` (T, K) fp32, ``step``
-    (T, K, Lt − 1) fp32, ``barred`` (T, K) int32, ``length`` (T, K) int32.  No host synchronisation beyond the batch structure's tables."""
+def graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="sequence_loss"):
+    """The graded forced pass up to the decoder's score matrix, then ``head``: the encoder side of the decode and the decoder once over all
+    positions of the T·K given captions, with gradients.  ``head`` is called inside the pass's ``enable_grad`` with a namespace — ``scores``
+    (T·K·Lt, ≥ C) fp32 (probabilities, or raw logits when ``logits``), ``cap_c`` the rows' column counts (an Idx), ``max_cols``, ``tgt``
+    (R, Lt) / ``length`` / ``finished`` (R,) int32 (``ops.force_inputs``'), ``steps`` the videos' sentence counts, ``plan`` the batch structure's plan, ``T``, ``K``, ``Lt`` — and
+    its result is returned.  ``weights``: what ``ops.check_scst`` is to check beside the captions (``sequence_loss``'s weights)."""
     (input_ids_list, video_features_list, input_masks_list, _tt, ingr_input_ids, _im, ingr_sep_masks, ingr_id_dict, oov_word_dict,
      _al, _ac, batch_step_num) = model_inputs
     ids, steps = ops.stack_captions(dec_seq_list)
     if ids.dim() == 2:
         ids = ids.unsqueeze(1)
     if steps != [int(s) for s in batch_step_num]:
-        raise ValueError("sequence_loss: the captions' rows per video %r are not the batch's step counts %r" % (steps, list(batch_step_num)))
+        raise ValueError("%s: the captions' rows per video %r are not the batch's step counts %r" % (who, steps, list(batch_step_num)))
     _, _, K = ops.check_scst(ids, baseline="none", lt=translator.max_t_len, steps=steps, weights=weights)
     model = translator.model
     cfg = model.config
     mode = cfg.model_mode
     dev = video_features_list[0].device
     if dev.type != "cuda":
-        raise ops._lib.SvpcKernelError("sequence_loss runs on the GPU only (no CPU fallback exists)")
+        raise ops._lib.SvpcKernelError("%s runs on the GPU only (no CPU fallback exists)" % who)
     N, L, F = video_features_list[0].shape
     S_pad = len(input_ids_list)
     Lt, D, V = cfg.max_t_len, cfg.hidden_size, cfg.vocab_size
@@ -125,9 +123,24 @@ def sequence_loss(translator, model_inputs, dec_seq_list, weights):
                 proj = _replicate(model.bank_projection(bank), K).contiguous()
                 bank = _replicate(bank, K).contiguous()
             scores = model._lm_probs(dec, bank, fp.ptr, cx, proj=proj)[0]
+        return head(SimpleNamespace(scores=scores, cap_c=fp.cap_c, max_cols=max(c_list), logits=mode == "video", tgt=tgt, length=length,
+                                    finished=_fin, steps=steps, plan=plan, T=T, K=K, Lt=Lt))
+
+
+def sequence_loss(translator, model_inputs, dec_seq_list, weights):
+    """The graded forced pass: loss = −Σ_{(t,k) not barred} w[t,k] · cum[t,k], cum the model's log-probability of the given caption
+    (``Translator.score_captions``'s ``cum`` under ``unk="bar"``), differentiable in every parameter the decode-conditions pass touches.
+    ``model_inputs`` as ``translate_batch`` takes them (only the video half is read, so the caller's ids and masks are left as they
+    are); ``dec_seq_list`` per video (S_b, K, Lt) or (S_b, Lt) int64 / int32 extended ids, 1 ≤ K ≤ 16; ``weights`` (T, K) or (T·K,)
+    floating point on the device (rounded to fp32).  ``model.train()``: dropout is on (the model's own RNG, advanced once per call);
+    ``model.eval()``: deterministic.  → a namespace: ``loss`` () fp32 (the only result with a gradient), ``cum`` (T, K) fp32, ``step``
+    (T, K, Lt − 1) fp32, ``barred`` (T, K) int32, ``length`` (T, K) int32.  No host synchronisation beyond the batch structure's tables."""
+    def head(p):
         w = weights.detach().reshape(-1).to(torch.float32).contiguous()
-        loss, cum, step, barred = ops.seq_nll(scores, fp.cap_c, tgt, length, w, mode == "video", UNK, max_cols=max(c_list))
-    return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K), length=length.view(T, K))
+        loss, cum, step, barred = ops.seq_nll(p.scores, p.cap_c, p.tgt, p.length, w, p.logits, UNK, max_cols=p.max_cols)
+        return SimpleNamespace(loss=loss, cum=cum.view(p.T, p.K), step=step.view(p.T, p.K, p.Lt - 1), barred=barred.view(p.T, p.K),
+                               length=p.length.view(p.T, p.K))
+    return graded_pass(translator, model_inputs, dec_seq_list, weights, head)
 
 
 class SelfCritical(object):
