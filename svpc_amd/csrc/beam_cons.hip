@@ -9,8 +9,9 @@
 // `a a b` the text `a a a b` does not complete it.  Restated by tests/constrained_beam_reference.py.
 //
 // Candidates of an unfinished parent h: svpc_beam_step_ctl's allowed columns, EOS also skipped while met(h) is not the full mask; of those
-// (a) the row's top-W by (raw, column) — phase one of beam_step_groups_kernel — and (b) its forced columns: phrase[cur][off] if a phrase is
-// in progress, else the first ids of all unmet phrases, each only if allowed and its child's cum' > −inf.  A column in both is one candidate.
+// (a) the row's top-W by (raw, column) — beam_common.h's topb_row, which leaves the list in every lane — and (b) its forced columns:
+// phrase[cur][off] if a phrase is in progress, else the first ids of all unmet phrases, each only if allowed and its child's cum' > −inf.
+// A column in both is one candidate.
 // A finished parent offers itself (PAD, cum and len kept, raw +inf).  Allocation (fairseq's stride over banks): live candidates (cum'
 // finite) rank inside their bank by svpc_beam_step_ctl's order (higher key, higher raw value, lower flat index h·C + c); the output order
 // is ascending (rank in bank, −bank); dead candidates follow in svpc_beam_step_ctl's total order; the first W become rows 0 … W − 1, missing
@@ -75,7 +76,7 @@ __device__ __forceinline__ bool cand_before(double ok, float orw, int of, double
 }
 
 template <int W>
-__global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a, ConsArgs ca) {
+__global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a, BeamCtl ctl, ConsArgs ca) {
     constexpr int NS = W + kConsMax;               // survivors of a row: its top-W columns and its forced columns
     constexpr int NC = W * NS;                     // … of a sentence (≤ 96)
     constexpr int kDead = -1, kNone = -2;          // c_bank of a dead candidate / of an empty entry
@@ -90,9 +91,8 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = t * W;
     const int pl = a.pos + 1;                      // position p of this step's pick
-    if (tid < W) {                                 // the parents' values, read before any write
-        p_cum[tid] = a.cum[r0 + tid]; p_fin[tid] = a.finished[r0 + tid]; p_len[tid] = a.len[r0 + tid]; p_st[tid] = ca.cstate[r0 + tid];
-    }
+    load_parents<W>(a, ctl.len, r0, tid, p_cum, p_fin, p_len);
+    if (tid < W) p_st[tid] = ca.cstate[r0 + tid];
     if (tid >= 64 && tid < 64 + kConsMax * kConsLen) ph[tid - 64] = ca.cons[(size_t)t * (kConsMax * kConsLen) + tid - 64];
     if (tid >= 128 && tid < 128 + kConsMax) {      // a phrase: the leading non-negative ids of its row
         const int* q = ca.cons + (size_t)t * (kConsMax * kConsLen) + (tid - 128) * kConsLen;
@@ -101,11 +101,7 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a
         plen[tid - 128] = n;
     }
     for (int e = tid; e < NC; e += kBeamThreads) c_flat[e] = INT_MAX;
-    if (a.ngram == 0 || pl < a.ngram) {
-        if (tid < W) n_ban[tid] = 0;
-    } else {
-        ngram_ban_rows<W>(a, r0, pl, lane, wave, ban, n_ban);
-    }
+    ngram_bans<W>(a, ctl, r0, pl, tid, ban, n_ban);
     __syncthreads();
     int M = 0;                                     // the constraints of the sentence: its leading non-empty rows
     while (M < kConsMax && plen[M] > 0) ++M;
@@ -118,32 +114,15 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a
             continue;
         }
         const Track k = unpack_state(p_st[h], plen, M);
-        const int skip_eos = (pl <= a.min_len || k.met != full) ? a.eos : a.unk;     // EOS is skipped like UNK: min length, unmet constraints
+        const int skip_eos = (pl <= ctl.min_len || k.met != full) ? a.eos : a.unk;     // EOS is skipped like UNK: min length, unmet constraints
         const float* row = a.scores + (size_t)r * a.ld;
         const double lse = a.logits ? row_lse(row, C, a.unk, lane) : 0.0;
         float val[W]; int idx[W];
-#pragma unroll
-        for (int q = 0; q < W; ++q) { val[q] = -INFINITY; idx[q] = INT_MAX; }
         const int nb = n_ban[h];
-        if (nb == 0) {
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk && c != skip_eos) topb_insert<W>(val, idx, row[c], c);
-        } else {
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk && c != skip_eos) topb_insert_ban<W>(val, idx, row[c], c, ban[h], nb);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {         // butterfly: lanes l and l^o hold disjoint sets, both end with their merged top-W
-            float ov[W]; int oi[W];
-#pragma unroll
-            for (int q = 0; q < W; ++q) { ov[q] = __shfl_xor(val[q], o, 64); oi[q] = __shfl_xor(idx[q], o, 64); }
-#pragma unroll
-            for (int q = 0; q < W; ++q) topb_insert<W>(val, idx, ov[q], oi[q]);
-        }
-        if (lane < W) {                            // every lane holds the row's top-W: lane q keeps entry q
-            float v = val[0]; int c = idx[0];
-#pragma unroll
-            for (int q = 1; q < W; ++q) if (lane == q) { v = val[q]; c = idx[q]; }
+        topb_row<W>(val, idx, C, lane, a.unk, skip_eos, RawKey{row}, BanList{ban[h], nb});
+        if (lane < W) {
+            float v; int c;
+            topb_entry<W>(val, idx, lane, v, c);
             if (c != INT_MAX) {
                 const int e = h * NS + lane;
                 c_step[e] = step_score(v, a.logits, lse); c_raw[e] = v; c_flat[e] = h * C + c; c_col[e] = c;
@@ -186,10 +165,10 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a
         if (fin) {
             const int ln = min(max(p_len[h], 0), a.ld_tok - 1);
             cu = p_cum[h]; raw = INFINITY; state = p_st[h];
-            key = a.lp ? (double)cu / a.lp[ln] : (double)cu;
+            key = ctl.lp ? (double)cu / ctl.lp[ln] : (double)cu;
         } else {
             cu = p_cum[h] + c_step[e]; raw = c_raw[e]; state = track_word(p_st[h], col, ph, plen, M);
-            key = a.lp ? (double)cu / a.lp[pl] : (double)cu;
+            key = ctl.lp ? (double)cu / ctl.lp[pl] : (double)cu;
         }
         bank = (cu > -INFINITY && cu < INFINITY) ? bank_of(state, plen, M) : kDead;
     }
@@ -219,79 +198,27 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_cons_kernel(BeamArgs a
             }
         }
     }
-    // tokens of a child: its parent's positions 0 … pos, then its own pick at pos + 1
     if (out < W) {
-        const int r = r0 + out;
-        const int C = a.row_c[r0 + h], X = a.row_x[r0 + h];
-        const int ext = fin ? a.pad : col;
-        const int mod = fin ? a.pad : (col >= C - X ? a.unk : col);
-        a.cum[r] = cu;
-        ca.cstate[r] = state;
-        a.finished[r] = (fin || ext == a.eos) ? 1 : 0;
-        a.len[r] = fin ? p_len[h] : pl;            // a finished parent keeps its length
-        a.parent[r] = r0 + h;
-        a.next_ext[r] = ext;
-        a.next_model[r] = mod;
-        a.text_out[(size_t)r * a.ld_tok + pl] = mod;
-        a.ext_out[(size_t)r * a.ld_tok + pl] = ext;
-        a.rows_out[(size_t)r * a.ld_tok + pl] = r * a.slot_rows + pl;
+        write_child(a, ctl.len, pl, r0 + out, r0 + h, col, fin, cu, fin ? p_len[h] : pl);     // (a finished parent keeps its length)
+        ca.cstate[r0 + out] = state;
         sel[out] = h;
     }
-    if (tid < W && tid >= n_cand) {                // fewer than W candidates: fill rows, as in svpc_beam_step
-        const int r = r0 + tid;
-        a.cum[r] = -INFINITY;
-        ca.cstate[r] = 0;
-        a.finished[r] = 1;
-        a.len[r] = pl;
-        a.parent[r] = r;
-        a.next_ext[r] = a.pad;
-        a.next_model[r] = a.pad;
-        a.text_out[(size_t)r * a.ld_tok + pl] = a.pad;
-        a.ext_out[(size_t)r * a.ld_tok + pl] = a.pad;
-        a.rows_out[(size_t)r * a.ld_tok + pl] = r * a.slot_rows + pl;
+    if (tid < W && tid >= n_cand) {                // fewer than W candidates: fill rows, as in beam_step_kernel
+        write_child(a, ctl.len, pl, r0 + tid, r0 + tid, a.pad, true, -INFINITY, pl);
+        ca.cstate[r0 + tid] = 0;
         sel[tid] = tid;
     }
     __syncthreads();
-    // phase three: the parents' rows
-    for (int i = tid; i < W * pl; i += kBeamThreads) {
-        const int q = i / pl, j = i - q * pl;
-        const size_t src = (size_t)(r0 + sel[q]) * a.ld_tok + j, dst = (size_t)(r0 + q) * a.ld_tok + j;
-        a.text_out[dst] = a.text_in[src];
-        a.ext_out[dst] = a.ext_in[src];
-        a.rows_out[dst] = a.rows_in[src];
-    }
-}
-
-// per sentence the n_best of its B final hypotheses: rows with cum = −inf last; otherwise more constraints met first, then the higher key
-// (double)cum / lp[len] (lp null: cum), then the lower beam index — a selection by strict comparison from beam 0 up
-__global__ __launch_bounds__(256) void beam_finalize_cons_kernel(const float* __restrict__ cum, const int* __restrict__ len,
-                                                                 const double* __restrict__ lp, const int* __restrict__ ext,
-                                                                 const int* __restrict__ cstate, int ld_tok, int n_sent, int B, int lt,
-                                                                 int n_best, int* __restrict__ best_ids, float* __restrict__ best_score,
-                                                                 int* __restrict__ best_len, int* __restrict__ best_met) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_sent) return;
-    unsigned taken = 0;
-    for (int k = 0; k < n_best; ++k) {
-        int hb = -1, tb = 0; double kb = 0.0;      // tb: the tier, 0 for cum = −inf, else 1 + the constraints met
-        for (int h = 0; h < B; ++h) {
-            if ((taken >> h) & 1u) continue;
-            const size_t i = (size_t)t * B + h;
-            const double key = lp ? (double)cum[i] / lp[min(max(len[i], 0), ld_tok - 1)] : (double)cum[i];
-            const int tier = cum[i] == -INFINITY ? 0 : 1 + __popc((unsigned)cstate[i] & 15u);
-            if (hb < 0 || tier > tb || (tier == tb && key > kb)) { kb = key; tb = tier; hb = h; }
-        }
-        taken |= 1u << hb;
-        const size_t i = (size_t)t * B + hb, o = (size_t)t * n_best + k;
-        best_score[o] = cum[i];
-        best_met[o] = cstate[i] & 15;
-        if (best_len) best_len[o] = len ? len[i] : 0;
-        const int* src = ext + i * ld_tok;
-        for (int j = 0; j < lt; ++j) best_ids[o * lt + j] = src[j];
-    }
+    copy_parent_rows<W>(a, r0, pl, tid, sel);
 }
 
 }  // namespace
+
+extern "C" int svpc_beam_finalize_cons(const float* cum, const int* len, const double* lp, const int* ext, const int* cstate, int ld_tok,
+                                       int n_sent, int beam, int lt, int n_best, int* best_ids, float* best_score, int* best_len,
+                                       int* best_met, hipStream_t stream) {
+    return beam_finalize<true>(cum, len, lp, ext, cstate, ld_tok, n_sent, beam, lt, n_best, best_ids, best_score, best_len, best_met, stream);
+}
 
 extern "C" int svpc_beam_step_cons(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int beam, int pos, int logits,
                                    int unk, int eos, int pad, int slot_rows, float* cum, int* finished, const int* text_in,
@@ -299,39 +226,13 @@ extern "C" int svpc_beam_step_cons(const float* scores, int ld, const int* row_c
                                    int* parent, int* next_ext, int* next_model, int min_len, int ngram, const unsigned* excl, int excl_v,
                                    const double* lp, int* len, const int* cons, int* cstate, hipStream_t stream) {
     if (n_sent == 0) return 0;
-    SVPC_REQUIRE(beam >= 1 && beam <= kBeamMax, "beam_step_cons: beam width must be 1..8");
-    SVPC_REQUIRE(pos >= 0 && pos + 1 < ld_tok && pos + 1 < slot_rows, "beam_step_cons: position pos + 1 must lie inside the token / ancestry rows");
-    SVPC_REQUIRE(text_in != text_out && ext_in != ext_out && rows_in != rows_out, "beam_step_cons: the token and ancestry tables are ping-pong pairs");
-    SVPC_REQUIRE(min_len >= 0 && min_len < ld_tok && ngram >= 0 && ngram < ld_tok, "beam_step_cons: min length and n-gram size must be 0..ld_tok-1");
-    SVPC_REQUIRE(ngram == 0 || ld_tok <= 64, "beam_step_cons: n-gram blocking holds a hypothesis's ids in one wave (ld_tok <= 64)");
+    BEAM_REQUIRE_COMMON("beam_step_cons");
+    BEAM_REQUIRE_CTL("beam_step_cons");
     SVPC_REQUIRE(len != nullptr && cons != nullptr && cstate != nullptr, "beam_step_cons: the length array, the constraint table and cstate are required");
-    SVPC_REQUIRE(excl == nullptr || excl_v > 0, "beam_step_cons: the exclusion bitmap needs its id count");
-    BeamArgs a{scores, ld, row_c, row_x, pos, logits, unk, eos, pad, slot_rows, cum, finished, text_in, ext_in, rows_in,
-               text_out, ext_out, rows_out, ld_tok, parent, next_ext, next_model, min_len, ngram, excl, excl_v, lp, len, nullptr, nullptr, 0};
-    ConsArgs ca{cons, cstate};
-    const dim3 grid(n_sent), block(kBeamThreads);
-    switch (beam) {
-        case 1: hipLaunchKernelGGL((beam_step_cons_kernel<1>), grid, block, 0, stream, a, ca); break;
-        case 2: hipLaunchKernelGGL((beam_step_cons_kernel<2>), grid, block, 0, stream, a, ca); break;
-        case 3: hipLaunchKernelGGL((beam_step_cons_kernel<3>), grid, block, 0, stream, a, ca); break;
-        case 4: hipLaunchKernelGGL((beam_step_cons_kernel<4>), grid, block, 0, stream, a, ca); break;
-        case 5: hipLaunchKernelGGL((beam_step_cons_kernel<5>), grid, block, 0, stream, a, ca); break;
-        case 6: hipLaunchKernelGGL((beam_step_cons_kernel<6>), grid, block, 0, stream, a, ca); break;
-        case 7: hipLaunchKernelGGL((beam_step_cons_kernel<7>), grid, block, 0, stream, a, ca); break;
-        default: hipLaunchKernelGGL((beam_step_cons_kernel<8>), grid, block, 0, stream, a, ca); break;
-    }
-    return svpc_check_launch("beam_step_cons");
-}
-
-extern "C" int svpc_beam_finalize_cons(const float* cum, const int* len, const double* lp, const int* ext, const int* cstate, int ld_tok,
-                                       int n_sent, int beam, int lt, int n_best, int* best_ids, float* best_score, int* best_len,
-                                       int* best_met, hipStream_t stream) {
-    if (n_sent == 0) return 0;
-    SVPC_REQUIRE(beam >= 1 && beam <= kBeamMax && lt >= 1 && lt <= ld_tok, "beam_finalize_cons: beam width 1..8, 1 <= lt <= ld_tok");
-    SVPC_REQUIRE(n_best >= 1 && n_best <= beam, "beam_finalize_cons: n_best must be 1..beam");
-    SVPC_REQUIRE(lp == nullptr || len != nullptr, "beam_finalize_cons: a length penalty needs the length array");
-    SVPC_REQUIRE(cstate != nullptr && best_met != nullptr, "beam_finalize_cons: cstate and best_met are required");
-    hipLaunchKernelGGL(beam_finalize_cons_kernel, dim3((n_sent + 255) / 256), dim3(256), 0, stream, cum, len, lp, ext, cstate, ld_tok, n_sent,
-                       beam, lt, n_best, best_ids, best_score, best_len, best_met);
-    return svpc_check_launch("beam_finalize_cons");
+    const BeamArgs a = BEAM_COMMON_ARGS;
+    const BeamCtl ctl{min_len, ngram, excl, excl_v, lp, len};
+    const ConsArgs ca{cons, cstate};
+    return beam_dispatch("beam_step_cons", beam, [&](auto w) {
+        hipLaunchKernelGGL((beam_step_cons_kernel<decltype(w)::value>), dim3(n_sent), dim3(kBeamThreads), 0, stream, a, ctl, ca);
+    });
 }

@@ -9,13 +9,14 @@
 // ranks by key = (double)aug' / lp[p] (lp null: aug'); a finished parent offers itself, token PAD, cum / aug / len kept, key
 // (double)aug / lp[len], raw value +inf, no penalty.  Group g's candidates — those of its Bg parents — rank by higher key, then higher raw
 // value, then lower flat index h·C + c (h the parent's row in the sentence, 0 … W − 1); the Bg best become rows g·Bg … g·Bg + Bg − 1, and
-// slots without a candidate are filled as in svpc_beam_step (parent the slot itself, PAD, cum = aug = −inf, finished, len p).  pen is a host
-// table (pen[n] = fp32(fp32(λ)·n), n < W): the kernel never multiplies by λ, so no contraction into an fma can change a bit.
+// slots without a candidate are fill rows (beam_common.h: write_child; parent the slot itself, PAD, cum = aug = −inf, finished, len p).
+// pen is a host table (pen[n] = fp32(fp32(λ)·n), n < W): the kernel never multiplies by λ, so no contraction into an fma can change a bit.
 //
 // Pruning: a penalised key is no longer monotone in the raw value within a row, but at most W − Bg distinct words carry a penalty, so a
 // column outside its row's top-W by (raw, column) has at least W better columns of which at least Bg are unpenalised: every row's top-W by
-// (raw, column) contains its top-Bg by penalised key, for every group.  So phase one is svpc_beam_step_ctl's with B = W — one wave per row,
-// register top-W, shuffle butterflies, an fp64 step score rounded once for the ≤ W·W survivors, left in LDS.  Phase two is one wave: lane
+// (raw, column) contains its top-Bg by penalised key, for every group.  So phase one is beam_common.h's topb_row with B = W — one wave per
+// row, register top-W, shuffle butterflies — and an fp64 step score rounded once for the ≤ W·W survivors, left in LDS.  Phase two is one
+// wave: lane
 // l holds candidate l of the current group (≤ Bg·W ≤ 64), counts its word among the picks of the earlier groups (lane i < W keeps the live
 // pick of output row i in a register), ranks itself against the group's other candidates by shuffles, and the Bg winners move to the lanes
 // of their output rows — no barrier between groups, no LDS or global traffic.  Phase three copies the parents' token and ancestry rows.
@@ -26,7 +27,7 @@ namespace {
 struct GroupArgs { int groups; const float* pen; float* aug; };
 
 template <int W>
-__global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs a, GroupArgs ga) {
+__global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs a, BeamCtl ctl, GroupArgs ga) {
     constexpr int NC = W * W;                      // survivors: the top-W columns of every row (≤ 64)
     __shared__ float c_step[NC], c_raw[NC];
     __shared__ int c_flat[NC], c_col[NC];
@@ -37,17 +38,12 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs
     const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = t * W;
     const int pl = a.pos + 1;                      // position p of this step's pick
-    if (tid < W) {
-        p_cum[tid] = a.cum[r0 + tid]; p_aug[tid] = ga.aug[r0 + tid]; p_fin[tid] = a.finished[r0 + tid]; p_len[tid] = a.len[r0 + tid];
-    }
+    load_parents<W>(a, ctl.len, r0, tid, p_cum, p_fin, p_len);
+    if (tid < W) p_aug[tid] = ga.aug[r0 + tid];
     if (tid < NC) c_flat[tid] = INT_MAX;
-    if (a.ngram == 0 || pl < a.ngram) {
-        if (tid < W) n_ban[tid] = 0;
-    } else {
-        ngram_ban_rows<W>(a, r0, pl, lane, wave, ban, n_ban);
-    }
+    ngram_bans<W>(a, ctl, r0, pl, tid, ban, n_ban);
     __syncthreads();
-    const int skip_eos = pl <= a.min_len ? a.eos : a.unk;     // min length: EOS is skipped like UNK
+    const int skip_eos = pl <= ctl.min_len ? a.eos : a.unk;     // min length: EOS is skipped like UNK
     // phase one: one wave per hypothesis row, its top-W columns by (raw, column) and their step scores
     for (int h = __builtin_amdgcn_readfirstlane(wave); h < W; h += kBeamThreads / 64) {
         const int r = r0 + h, C = a.row_c[r];
@@ -58,28 +54,10 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs
         const float* row = a.scores + (size_t)r * a.ld;
         const double lse = a.logits ? row_lse(row, C, a.unk, lane) : 0.0;
         float val[W]; int idx[W];
-#pragma unroll
-        for (int k = 0; k < W; ++k) { val[k] = -INFINITY; idx[k] = INT_MAX; }
-        const int nb = n_ban[h];
-        if (nb == 0) {
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk && c != skip_eos) topb_insert<W>(val, idx, row[c], c);
-        } else {
-            for (int c = lane; c < C; c += 64)
-                if (c != a.unk && c != skip_eos) topb_insert_ban<W>(val, idx, row[c], c, ban[h], nb);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {         // butterfly: lanes l and l^o hold disjoint sets, both end with their merged top-W
-            float ov[W]; int oi[W];
-#pragma unroll
-            for (int k = 0; k < W; ++k) { ov[k] = __shfl_xor(val[k], o, 64); oi[k] = __shfl_xor(idx[k], o, 64); }
-#pragma unroll
-            for (int k = 0; k < W; ++k) topb_insert<W>(val, idx, ov[k], oi[k]);
-        }
-        if (lane < W) {                            // every lane holds the row's top-W: lane k keeps entry k
-            float v = val[0]; int c = idx[0];
-#pragma unroll
-            for (int k = 1; k < W; ++k) if (lane == k) { v = val[k]; c = idx[k]; }
+        topb_row<W>(val, idx, C, lane, a.unk, skip_eos, RawKey{row}, BanList{ban[h], n_ban[h]});
+        if (lane < W) {
+            float v; int c;
+            topb_entry<W>(val, idx, lane, v, c);
             if (c != INT_MAX) {
                 const int e = h * W + lane;
                 c_step[e] = step_score(v, a.logits, lse); c_raw[e] = v; c_flat[e] = h * C + c; c_col[e] = c;
@@ -108,12 +86,12 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs
             if (fin) {
                 const int ln = min(max(p_len[h], 0), a.ld_tok - 1);
                 cu = p_cum[h]; au = p_aug[h]; raw = INFINITY;
-                key = a.lp ? (double)au / a.lp[ln] : (double)au;
+                key = ctl.lp ? (double)au / ctl.lp[ln] : (double)au;
             } else if (valid) {
                 const float st = c_step[e];
                 const float s = p_aug[h] + st;
                 cu = p_cum[h] + st; au = s - ga.pen[n]; raw = c_raw[e];
-                key = a.lp ? (double)au / a.lp[pl] : (double)au;
+                key = ctl.lp ? (double)au / ctl.lp[pl] : (double)au;
             }
             int rank = 0;                          // the group's candidates ahead of this one (a strict total order)
             for (int j = 0; j < ng; ++j) {
@@ -132,34 +110,16 @@ __global__ __launch_bounds__(kBeamThreads) void beam_step_groups_kernel(BeamArgs
                 }
             }
         }
-        // tokens of a child: its parent's positions 0 … pos, then its own pick at pos + 1
         if (lane < W) {
             const int r = r0 + lane, h = o_par;
-            const int C = a.row_c[r0 + h], X = a.row_x[r0 + h];
-            const bool was_fin = o_fin != 0;       // a finished parent, or a fill row
-            const int ext = was_fin ? a.pad : o_col;
-            const int mod = was_fin ? a.pad : (o_col >= C - X ? a.unk : o_col);
-            a.cum[r] = o_cum;
+            const bool kept = o_has && p_fin[h];  // a finished parent keeps its length
+            write_child(a, ctl.len, pl, r, r0 + h, o_col, o_fin != 0, o_cum, kept ? p_len[h] : pl);     // (o_fin: a finished parent, or a fill row)
             ga.aug[r] = o_aug;
-            a.finished[r] = (was_fin || ext == a.eos) ? 1 : 0;
-            a.len[r] = (o_has && p_fin[h]) ? p_len[h] : pl;     // a finished parent keeps its length
-            a.parent[r] = r0 + h;
-            a.next_ext[r] = ext;
-            a.next_model[r] = mod;
-            a.text_out[(size_t)r * a.ld_tok + pl] = mod;
-            a.ext_out[(size_t)r * a.ld_tok + pl] = ext;
-            a.rows_out[(size_t)r * a.ld_tok + pl] = r * a.slot_rows + pl;
             sel[lane] = h;
         }
     }
     __syncthreads();
-    for (int e = tid; e < W * pl; e += kBeamThreads) {
-        const int k = e / pl, j = e - k * pl;
-        const size_t src = (size_t)(r0 + sel[k]) * a.ld_tok + j, dst = (size_t)(r0 + k) * a.ld_tok + j;
-        a.text_out[dst] = a.text_in[src];
-        a.ext_out[dst] = a.ext_in[src];
-        a.rows_out[dst] = a.rows_in[src];
-    }
+    copy_parent_rows<W>(a, r0, pl, tid, sel);
 }
 
 }  // namespace
@@ -170,27 +130,14 @@ extern "C" int svpc_beam_step_groups(const float* scores, int ld, const int* row
                                      int* parent, int* next_ext, int* next_model, int min_len, int ngram, const unsigned* excl, int excl_v,
                                      const double* lp, int* len, int groups, const float* pen, float* aug, hipStream_t stream) {
     if (n_sent == 0) return 0;
-    SVPC_REQUIRE(beam >= 1 && beam <= kBeamMax, "beam_step_groups: beam width must be 1..8");
+    BEAM_REQUIRE_COMMON("beam_step_groups");
+    BEAM_REQUIRE_CTL("beam_step_groups");
     SVPC_REQUIRE(groups >= 1 && beam % groups == 0, "beam_step_groups: the number of groups must divide the beam width");
-    SVPC_REQUIRE(pos >= 0 && pos + 1 < ld_tok && pos + 1 < slot_rows, "beam_step_groups: position pos + 1 must lie inside the token / ancestry rows");
-    SVPC_REQUIRE(text_in != text_out && ext_in != ext_out && rows_in != rows_out, "beam_step_groups: the token and ancestry tables are ping-pong pairs");
-    SVPC_REQUIRE(min_len >= 0 && min_len < ld_tok && ngram >= 0 && ngram < ld_tok, "beam_step_groups: min length and n-gram size must be 0..ld_tok-1");
-    SVPC_REQUIRE(ngram == 0 || ld_tok <= 64, "beam_step_groups: n-gram blocking holds a hypothesis's ids in one wave (ld_tok <= 64)");
     SVPC_REQUIRE(len != nullptr && pen != nullptr && aug != nullptr, "beam_step_groups: the length array, the penalty table and aug are required");
-    SVPC_REQUIRE(excl == nullptr || excl_v > 0, "beam_step_groups: the exclusion bitmap needs its id count");
-    BeamArgs a{scores, ld, row_c, row_x, pos, logits, unk, eos, pad, slot_rows, cum, finished, text_in, ext_in, rows_in,
-               text_out, ext_out, rows_out, ld_tok, parent, next_ext, next_model, min_len, ngram, excl, excl_v, lp, len, nullptr, nullptr, 0};
-    GroupArgs ga{groups, pen, aug};
-    const dim3 grid(n_sent), block(kBeamThreads);
-    switch (beam) {
-        case 1: hipLaunchKernelGGL((beam_step_groups_kernel<1>), grid, block, 0, stream, a, ga); break;
-        case 2: hipLaunchKernelGGL((beam_step_groups_kernel<2>), grid, block, 0, stream, a, ga); break;
-        case 3: hipLaunchKernelGGL((beam_step_groups_kernel<3>), grid, block, 0, stream, a, ga); break;
-        case 4: hipLaunchKernelGGL((beam_step_groups_kernel<4>), grid, block, 0, stream, a, ga); break;
-        case 5: hipLaunchKernelGGL((beam_step_groups_kernel<5>), grid, block, 0, stream, a, ga); break;
-        case 6: hipLaunchKernelGGL((beam_step_groups_kernel<6>), grid, block, 0, stream, a, ga); break;
-        case 7: hipLaunchKernelGGL((beam_step_groups_kernel<7>), grid, block, 0, stream, a, ga); break;
-        default: hipLaunchKernelGGL((beam_step_groups_kernel<8>), grid, block, 0, stream, a, ga); break;
-    }
-    return svpc_check_launch("beam_step_groups");
+    const BeamArgs a = BEAM_COMMON_ARGS;
+    const BeamCtl ctl{min_len, ngram, excl, excl_v, lp, len};
+    const GroupArgs ga{groups, pen, aug};
+    return beam_dispatch("beam_step_groups", beam, [&](auto w) {
+        hipLaunchKernelGGL((beam_step_groups_kernel<decltype(w)::value>), dim3(n_sent), dim3(kBeamThreads), 0, stream, a, ctl, ga);
+    });
 }

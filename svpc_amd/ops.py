@@ -2292,6 +2292,48 @@ def exclusion_bitmap(tokens, vocab, device):
     return torch.tensor([w - (1 << 32) if w >= 1 << 31 else w for w in words], dtype=torch.int32, device=device)
 
 
+def _beam_step_shared(fn, scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows):
+    """What the four selection steps check and build alike (``fn``: the caller's name, for the error texts) → ((R, Lt, device), the
+    (parent, next_ext, next_model) outputs, the 24 leading arguments of the library call)."""
+    if not 1 <= beam <= BEAM_MAX:
+        raise ValueError("%s: beam width must be 1..%d" % (fn, BEAM_MAX))
+    R, dev = cum.shape[0], scores.device
+    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be fp32 (T·beam, C) rows with unit column stride" % fn)
+    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
+        raise ValueError("%s: cum fp32 and finished int32, both contiguous (T·beam,)" % fn)
+    lt = toks_in[0].shape[1]
+    for m in tuple(toks_in) + tuple(toks_out):
+        if not _id_rows(m, R, lt, dev):
+            raise ValueError("%s: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device" % fn)
+    if any(i.data_ptr() == o.data_ptr() for i, o in zip(toks_in, toks_out)):
+        raise ValueError("%s: the token and ancestry tables are ping-pong pairs" % fn)
+    if not 0 <= pos < lt - 1 or slot_rows < lt:
+        raise ValueError("%s: position %d outside the %d-column tables" % (fn, pos, lt))
+    outs = tuple(torch.empty(R, dtype=torch.int32, device=dev) for _ in range(3))
+    args = [_p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
+            1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
+            _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(outs[0]), _p(outs[1]), _p(outs[2])]
+    return (R, lt, dev), outs, args
+
+
+def _beam_step_controls(fn, R, lt, dev, length, min_length, block_ngram_repeat, lp, exclusion, need_length=True):
+    """The decoding controls of a selection step, checked → their six arguments of the library call."""
+    if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
+        raise ValueError("%s: min_length and block_ngram_repeat must be 0..%d" % (fn, lt - 1))
+    if block_ngram_repeat and lt > 64:
+        raise ValueError("%s: block_ngram_repeat needs Lt <= 64" % fn)
+    if (length is None and need_length) or (length is not None and not _row_vec(length, R, torch.int32, dev)):
+        raise ValueError("%s: length must be contiguous int32 (T·beam,) on the scores' device" % fn)
+    if lp is not None and (length is None or not _lp_table(lp, lt, dev)):
+        raise ValueError("%s: lp must be a contiguous float64 table of >= Lt entries on the scores' device, with length" % fn)
+    bits, vocab = exclusion if exclusion is not None else (None, 0)
+    if exclusion is not None and (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1
+                                  or not bits.is_contiguous() or bits.device != dev):
+        raise ValueError("%s: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device" % fn)
+    return [int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length)]
+
+
 def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in, toks_out, slot_rows, *, length=None,
               min_length=0, block_ngram_repeat=0, exclusion=None, lp=None, history=None):
     """One beam-search selection step (svpc_beam_step) over ``scores`` (T·beam, ≥ C) — probabilities, or logits when ``logits``.
@@ -2304,26 +2346,18 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
     (table, desc, bos): ``table`` a contiguous int32 (rows, Lt) matrix of earlier sentences' chosen extended ids on the scores' device,
     ``desc`` 2·T host ints (an Idx or a list) — sentence t's history is rows desc[2t] … desc[2t] + desc[2t + 1] − 1 — and the BOS id.
     → (parent, next_ext, next_model) int32 (T·beam,)."""
-    if not 1 <= beam <= BEAM_MAX:
-        raise ValueError("beam_step: beam width must be 1..%d" % BEAM_MAX)
-    R = cum.shape[0]
-    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
-        raise ValueError("beam_step: scores must be fp32 (T·beam, C) rows with unit column stride")
-    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
-        raise ValueError("beam_step: cum fp32 and finished int32, both contiguous (T·beam,)")
-    lt = toks_in[0].shape[1]
-    for m in tuple(toks_in) + tuple(toks_out):
-        if not _id_rows(m, R, lt, scores.device):
-            raise ValueError("beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
-    if not 0 <= pos < lt - 1 or slot_rows < lt:
-        raise ValueError("beam_step: position %d outside the %d-column tables" % (pos, lt))
-    ctl = length is not None or min_length or block_ngram_repeat or exclusion is not None or lp is not None or history is not None
+    (R, lt, dev), outs, args = _beam_step_shared("beam_step", scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished, toks_in,
+                                                 toks_out, slot_rows)
+    ctl = _beam_step_controls("beam_step", R, lt, dev, length, min_length, block_ngram_repeat, lp, exclusion, need_length=False)
+    name = "beam_step"
+    if length is not None or min_length or block_ngram_repeat or exclusion is not None or lp is not None or history is not None:
+        name, args = "beam_step_ctl", args + ctl
     if history is not None:
         table, desc, bos = history
         desc = as_idx(desc)
         if int(block_ngram_repeat) < 1 or lt > 64:
             raise ValueError("beam_step: paragraph scope needs block_ngram_repeat >= 1 and Lt <= 64")
-        if table.dim() != 2 or not _id_rows(table, table.shape[0], lt, scores.device):
+        if table.dim() != 2 or not _id_rows(table, table.shape[0], lt, dev):
             raise ValueError("beam_step: the history must be a contiguous int32 (rows, Lt) matrix on the scores' device")
         d = desc.host
         if len(d) != 2 * (R // beam) or any(c < 0 or f < 0 or f + c > table.shape[0] for f, c in zip(d[0::2], d[1::2])):
@@ -2331,36 +2365,10 @@ def beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finis
         rc = as_idx(row_c).host
         if rc and max(rc) > SAMPLE_COLS_MAX:
             raise ValueError("beam_step: paragraph scope reads rows of at most %d columns" % SAMPLE_COLS_MAX)
-    if ctl:
-        if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
-            raise ValueError("beam_step: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
-        if block_ngram_repeat and lt > 64:
-            raise ValueError("beam_step: block_ngram_repeat needs Lt <= 64")
-        if length is not None and not _row_vec(length, R, torch.int32, scores.device):
-            raise ValueError("beam_step: length must be contiguous int32 (T·beam,) on the scores' device")
-        if lp is not None and (length is None or not _lp_table(lp, lt, scores.device)):
-            raise ValueError("beam_step: lp must be a contiguous float64 table of >= Lt entries on the scores' device, with length")
-        if exclusion is not None:
-            bits, vocab = exclusion
-            if (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1 or not bits.is_contiguous()
-                    or bits.device != scores.device):
-                raise ValueError("beam_step: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
-    _need_gpu(scores)
-    dev = scores.device
-    parent = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt = torch.empty(R, dtype=torch.int32, device=dev)
-    args = [_p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
-            1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
-            _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt)]
-    name = "beam_step"
-    if ctl:
-        bits, vocab = exclusion if exclusion is not None else (None, 0)
-        name, args = "beam_step_ctl", args + [int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length)]
-    if history is not None:
         name, args = "beam_step_para", args + [_p(table), _p(desc.dev(dev)), int(bos)]
+    _need_gpu(scores)
     _lib.call(name, *args, _stream())
-    return parent, nxt_ext, nxt
+    return outs
 
 
 def check_diverse(beam, num_groups, diversity_strength, n_best=None):
@@ -2403,47 +2411,18 @@ def beam_step_groups(scores, row_c, row_x, beam, groups, pos, logits, unk, eos, 
     sentence in ``groups`` groups (row g·Bg + j: hypothesis j of group g), the groups picking in order under the Hamming penalty table
     ``pen`` (fp32 (≥ beam,), ``diversity_table``).  In place: ``cum`` (the model's score), ``aug`` (the selection score, fp32
     (T·beam,)), ``finished``, ``length`` (required).  → (parent, next_ext, next_model) int32 (T·beam,)."""
-    if not 1 <= beam <= BEAM_MAX:
-        raise ValueError("beam_step_groups: beam width must be 1..%d" % BEAM_MAX)
+    (R, lt, dev), outs, args = _beam_step_shared("beam_step_groups", scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished,
+                                                 toks_in, toks_out, slot_rows)
+    ctl = _beam_step_controls("beam_step_groups", R, lt, dev, length, min_length, block_ngram_repeat, lp, exclusion)
     if isinstance(groups, bool) or not isinstance(groups, numbers.Integral) or groups < 1 or beam % groups:
         raise ValueError("beam_step_groups: the number of groups must divide the beam width")
-    R = cum.shape[0]
-    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
-        raise ValueError("beam_step_groups: scores must be fp32 (T·beam, C) rows with unit column stride")
-    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
-        raise ValueError("beam_step_groups: cum fp32 and finished int32, both contiguous (T·beam,)")
-    if not _row_vec(aug, R, torch.float32, scores.device) or aug.data_ptr() == cum.data_ptr():
+    if not _row_vec(aug, R, torch.float32, dev) or aug.data_ptr() == cum.data_ptr():
         raise ValueError("beam_step_groups: aug must be contiguous fp32 (T·beam,) on the scores' device, and not cum itself")
-    if pen.dtype != torch.float32 or pen.dim() != 1 or pen.shape[0] < beam or not pen.is_contiguous() or pen.device != scores.device:
+    if pen.dtype != torch.float32 or pen.dim() != 1 or pen.shape[0] < beam or not pen.is_contiguous() or pen.device != dev:
         raise ValueError("beam_step_groups: pen must be a contiguous fp32 table of >= beam entries on the scores' device")
-    lt = toks_in[0].shape[1]
-    for m in tuple(toks_in) + tuple(toks_out):
-        if not _id_rows(m, R, lt, scores.device):
-            raise ValueError("beam_step_groups: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
-    if not 0 <= pos < lt - 1 or slot_rows < lt:
-        raise ValueError("beam_step_groups: position %d outside the %d-column tables" % (pos, lt))
-    if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
-        raise ValueError("beam_step_groups: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
-    if block_ngram_repeat and lt > 64:
-        raise ValueError("beam_step_groups: block_ngram_repeat needs Lt <= 64")
-    if length is None or not _row_vec(length, R, torch.int32, scores.device):
-        raise ValueError("beam_step_groups: length must be contiguous int32 (T·beam,) on the scores' device")
-    if lp is not None and not _lp_table(lp, lt, scores.device):
-        raise ValueError("beam_step_groups: lp must be a contiguous float64 table of >= Lt entries on the scores' device")
-    bits, vocab = exclusion if exclusion is not None else (None, 0)
-    if exclusion is not None and (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1
-                                  or not bits.is_contiguous() or bits.device != scores.device):
-        raise ValueError("beam_step_groups: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
     _need_gpu(scores)
-    dev = scores.device
-    parent = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt = torch.empty(R, dtype=torch.int32, device=dev)
-    _lib.call("beam_step_groups", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
-              int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
-              _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
-              int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), int(groups), _p(pen), _p(aug), _stream())
-    return parent, nxt_ext, nxt
+    _lib.call("beam_step_groups", *args, *ctl, int(groups), _p(pen), _p(aug), _stream())
+    return outs
 
 
 def check_stochastic_beam(max_t_len, beam_size, seed=None, max_cols=None, random_sampling_temp=1.0, min_length=0):
@@ -2482,39 +2461,22 @@ def stochastic_beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad,
     host copy).  → (parent, next_ext, next_model) int32 (T·beam,)."""
     if isinstance(beam, bool) or not isinstance(beam, numbers.Integral) or not 1 <= beam <= BEAM_MAX:
         raise ValueError("stochastic_beam_step: beam width must be 1..%d" % BEAM_MAX)
-    R = cum.shape[0]
-    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
-        raise ValueError("stochastic_beam_step: scores must be fp32 (T·beam, C) rows with unit column stride")
+    (R, lt, dev), outs, args = _beam_step_shared("stochastic_beam_step", scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished,
+                                                 toks_in, toks_out, slot_rows)
     for t, dt in ((cum, torch.float32), (phi, torch.float64), (gkey, torch.float64), (finished, torch.int32), (length, torch.int32)):
-        if not _row_vec(t, R, dt, scores.device):
+        if not _row_vec(t, R, dt, dev):
             raise ValueError("stochastic_beam_step: cum fp32, phi and gkey float64, finished and length int32, all contiguous (T·beam,) "
                              "on the scores' device")
-    lt = toks_in[0].shape[1]
-    for m in tuple(toks_in) + tuple(toks_out):
-        if not _id_rows(m, R, lt, scores.device):
-            raise ValueError("stochastic_beam_step: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
-    if any(i.data_ptr() == o.data_ptr() for i, o in zip(toks_in, toks_out)):
-        raise ValueError("stochastic_beam_step: the token and ancestry tables are ping-pong pairs")
-    if not 0 <= pos < lt - 1 or slot_rows < lt:
-        raise ValueError("stochastic_beam_step: position %d outside the %d-column tables" % (pos, lt))
-    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
+    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != dev:
         raise ValueError("stochastic_beam_step: seed must be a device int64 tensor")
     if not (math.isfinite(temp) and temp > 0 and 0 <= int(min_length) < lt):
         raise ValueError("stochastic_beam_step: temp finite > 0, min_length 0..Lt-1")
-    rc = as_idx(row_c)
-    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    max_c = int(max_cols) if max_cols is not None else (max(as_idx(row_c).host) if R else 1)
     if max_c > SAMPLE_COLS_MAX or max_c > scores.shape[1] or max_c < 1:
         raise ValueError("stochastic_beam_step: rows of 1..%d columns, inside the score matrix" % SAMPLE_COLS_MAX)
     _need_gpu(scores)
-    dev = scores.device
-    parent = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt = torch.empty(R, dtype=torch.int32, device=dev)
-    _lib.call("beam_step_gumbel", _p(scores), scores.stride(0), _p(rc.dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam), int(pos),
-              1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]), _p(toks_in[1]),
-              _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt), float(temp),
-              int(min_length), _p(seed), _p(phi), _p(gkey), _p(length), int(max_c), _stream())
-    return parent, nxt_ext, nxt
+    _lib.call("beam_step_gumbel", *args, float(temp), int(min_length), _p(seed), _p(phi), _p(gkey), _p(length), int(max_c), _stream())
+    return outs
 
 
 CONS_MAX = 4                    # constraints (phrases) of a sentence
@@ -2575,63 +2537,20 @@ def beam_step_cons(scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, 
     to CONS_MAX phrases that a caption must contain — ``cons`` the (T, CONS_MAX, CONS_LEN) int32 device table of ``check_constraints``,
     ``cstate`` (T·beam,) int32 the rows' tracker states (start 0).  In place: ``cum``, ``cstate``, ``finished``, ``length`` (required).
     → (parent, next_ext, next_model) int32 (T·beam,)."""
-    if not 1 <= beam <= BEAM_MAX:
-        raise ValueError("beam_step_cons: beam width must be 1..%d" % BEAM_MAX)
-    R = cum.shape[0]
-    if scores.dim() != 2 or scores.shape[0] != R or R % beam or scores.stride(1) != 1 or scores.dtype != torch.float32:
-        raise ValueError("beam_step_cons: scores must be fp32 (T·beam, C) rows with unit column stride")
-    if not (_row_vec(cum, R, torch.float32) and _row_vec(finished, R, torch.int32)):
-        raise ValueError("beam_step_cons: cum fp32 and finished int32, both contiguous (T·beam,)")
-    _check_cons("beam_step_cons", cons, cstate, R // beam, R, scores.device)
-    lt = toks_in[0].shape[1]
-    for m in tuple(toks_in) + tuple(toks_out):
-        if not _id_rows(m, R, lt, scores.device):
-            raise ValueError("beam_step_cons: token / ancestry tables must be contiguous int32 (T·beam, Lt) on the scores' device")
-    if not 0 <= pos < lt - 1 or slot_rows < lt:
-        raise ValueError("beam_step_cons: position %d outside the %d-column tables" % (pos, lt))
-    if not (0 <= int(min_length) < lt and 0 <= int(block_ngram_repeat) < lt):
-        raise ValueError("beam_step_cons: min_length and block_ngram_repeat must be 0..%d" % (lt - 1))
-    if block_ngram_repeat and lt > 64:
-        raise ValueError("beam_step_cons: block_ngram_repeat needs Lt <= 64")
-    if length is None or not _row_vec(length, R, torch.int32, scores.device):
-        raise ValueError("beam_step_cons: length must be contiguous int32 (T·beam,) on the scores' device")
-    if lp is not None and not _lp_table(lp, lt, scores.device):
-        raise ValueError("beam_step_cons: lp must be a contiguous float64 table of >= Lt entries on the scores' device")
-    bits, vocab = exclusion if exclusion is not None else (None, 0)
-    if exclusion is not None and (bits.dtype != torch.int32 or bits.dim() != 1 or bits.shape[0] * 32 < vocab or vocab < 1
-                                  or not bits.is_contiguous() or bits.device != scores.device):
-        raise ValueError("beam_step_cons: exclusion must be (int32 bitmap of >= vocab bits, vocab) on the scores' device")
+    (R, lt, dev), outs, args = _beam_step_shared("beam_step_cons", scores, row_c, row_x, beam, pos, logits, unk, eos, pad, cum, finished,
+                                                 toks_in, toks_out, slot_rows)
+    ctl = _beam_step_controls("beam_step_cons", R, lt, dev, length, min_length, block_ngram_repeat, lp, exclusion)
+    _check_cons("beam_step_cons", cons, cstate, R // beam, R, dev)
     _need_gpu(scores)
-    dev = scores.device
-    parent = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
-    nxt = torch.empty(R, dtype=torch.int32, device=dev)
-    _lib.call("beam_step_cons", _p(scores), scores.stride(0), _p(as_idx(row_c).dev(dev)), _p(as_idx(row_x).dev(dev)), R // beam, int(beam),
-              int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(cum), _p(finished), _p(toks_in[0]),
-              _p(toks_in[1]), _p(toks_in[2]), _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(parent), _p(nxt_ext), _p(nxt),
-              int(min_length), int(block_ngram_repeat), _p(bits), int(vocab), _p(lp), _p(length), _p(cons), _p(cstate), _stream())
-    return parent, nxt_ext, nxt
+    _lib.call("beam_step_cons", *args, *ctl, _p(cons), _p(cstate), _stream())
+    return outs
 
 
 def beam_finalize_cons(cum, ext, beam, n_best, cstate, length=None, lp=None):
     """→ (ids (T, n_best, Lt) int32, score (T, n_best) fp32, len (T, n_best) int32, met (T, n_best) int32): ``beam_finalize_nbest`` in the
     order of constrained beam search — rows with cum = −inf last; above them more constraints met (bits 0–3 of ``cstate``) first, then the
     higher (double)cum / lp[len], then the lower beam index — svpc_beam_finalize_cons."""
-    T, lt = _check_finalize(cum, ext, beam, n_best)
-    if length is not None and not _row_vec(length, T * beam, torch.int32):
-        raise ValueError("beam_finalize_cons: length must be contiguous int32 (T·beam,)")
-    if lp is not None and (length is None or not _lp_table(lp, lt)):
-        raise ValueError("beam_finalize_cons: lp must be a contiguous float64 table of >= Lt entries, with length")
-    if not _row_vec(cstate, T * beam, torch.int32, ext.device):
-        raise ValueError("beam_finalize_cons: cstate must be contiguous int32 (T·beam,) on the ids' device")
-    _need_gpu(ext)
-    ids = torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device)
-    score = torch.empty(T, n_best, dtype=torch.float32, device=ext.device)
-    ln = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
-    met = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
-    _lib.call("beam_finalize_cons", _p(cum), _p(length), _p(lp), _p(ext), _p(cstate), lt, T, int(beam), lt, int(n_best), _p(ids), _p(score),
-              _p(ln), _p(met), _stream())
-    return ids, score, ln, met
+    return _beam_finalize_nbest("beam_finalize_cons", cum, ext, beam, n_best, length, lp, cstate)
 
 
 def _check_finalize(cum, ext, beam, n_best=1):
@@ -2660,18 +2579,24 @@ def beam_finalize_nbest(cum, ext, beam, n_best, length=None, lp=None):
     """→ (ids (T, n_best, Lt) int32, score (T, n_best) fp32, len (T, n_best) int32): per sentence its ``n_best`` hypotheses in order of
     (double)cum / lp[len] (``lp`` None: cum), ties to the lower beam index — svpc_beam_finalize_nbest.  ``length`` (T·beam,) int32 (needed
     with ``lp``; None: len 0)."""
+    return _beam_finalize_nbest("beam_finalize", cum, ext, beam, n_best, length, lp)
+
+
+def _beam_finalize_nbest(fn, cum, ext, beam, n_best, length, lp, *cstate):
+    """the body of the two n-best picks: ``cstate`` given → svpc_beam_finalize_cons and a fourth output, the constraints met"""
     T, lt = _check_finalize(cum, ext, beam, n_best)
     if length is not None and not _row_vec(length, T * beam, torch.int32):
-        raise ValueError("beam_finalize: length must be contiguous int32 (T·beam,)")
+        raise ValueError("%s: length must be contiguous int32 (T·beam,)" % fn)
     if lp is not None and (length is None or not _lp_table(lp, lt)):
-        raise ValueError("beam_finalize: lp must be a contiguous float64 table of >= Lt entries, with length")
+        raise ValueError("%s: lp must be a contiguous float64 table of >= Lt entries, with length" % fn)
+    if cstate and not _row_vec(cstate[0], T * beam, torch.int32, ext.device):
+        raise ValueError("%s: cstate must be contiguous int32 (T·beam,) on the ids' device" % fn)
     _need_gpu(ext)
-    ids = torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device)
-    score = torch.empty(T, n_best, dtype=torch.float32, device=ext.device)
-    ln = torch.empty(T, n_best, dtype=torch.int32, device=ext.device)
-    _lib.call("beam_finalize_nbest", _p(cum), _p(length), _p(lp), _p(ext), lt, T, int(beam), lt, int(n_best), _p(ids), _p(score), _p(ln),
-              _stream())
-    return ids, score, ln
+    outs = [torch.empty(T, n_best, lt, dtype=torch.int32, device=ext.device), torch.empty(T, n_best, dtype=torch.float32, device=ext.device)]
+    outs += [torch.empty(T, n_best, dtype=torch.int32, device=ext.device) for _ in range(1 + len(cstate))]      # len [, met]
+    _lib.call("beam_finalize_cons" if cstate else "beam_finalize_nbest", _p(cum), _p(length), _p(lp), _p(ext), *map(_p, cstate), lt, T,
+              int(beam), lt, int(n_best), *map(_p, outs), _stream())
+    return tuple(outs)
 
 
 SAMPLE_COLS_MAX = 4096          # columns of a sample row (the draw index is r·4096 + c)
