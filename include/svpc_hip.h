@@ -593,6 +593,18 @@ int svpc_sample_step(const float* scores, int ld, const int* row_c, const int* r
 /* the seed of one sampling decode, on the device: src = (fixed, value); fixed != 0: *used = value; otherwise *used is drawn from the
  * decode's seed word *word, which advances (consecutive replays of one captured decode draw different streams) */
 int svpc_sample_seed(const long long* src, long long* word, long long* used, svpc_stream_t stream);
+/* ---- ensemble decoding (OpenNMT's EnsembleModel / avg_raw_probs; the reference vendored its decode strategies without it): n_members
+ * (1..8) models deliver one fp32 score matrix each for the same n_rows hypothesis rows, and the step kernels above see ONE matrix.
+ * scores / ld / weights are HOST arrays of n_members device pointers, leading dimensions and fp64 weights (finite, >= 0, not all 0; the
+ * caller normalises them to sum 1); they are copied into the kernel's by-value arguments, so there is no table in device memory and a
+ * captured decode replays the launch unchanged.  A member with weight 0 is never read.  Row r has C = row_c[r / rows_per] <= max_c columns
+ * (max_c 1..4096, within every ld and ld_out).  Member probability p (fp64): logits == 0: raw > 0 ? raw : 0; logits != 0: exp(raw − lse),
+ * lse the log-sum-exp of the member row's columns c < C, c != unk, with p[unk] = 0 and a row without a finite logit contributing 0.
+ * rule 0 ("prob"): out = fp32(sum_m w_m·p_m), terms in ascending m, multiply and add rounded separately; rule 1 ("logprob"): out =
+ * fp32(exp(sum_m w_m·log p_m)), 0 once a counted member has p = 0, not renormalised.  Columns C <= c < ld_out are written 0.  out is a
+ * PROBABILITY matrix in both modes: the step kernels take it with logits = 0.  n_rows == 0 returns 0. */
+int svpc_ensemble_combine(const float* const* scores, const int* ld, const double* weights, int n_members, const int* row_c, int rows_per,
+                          int n_rows, int max_c, int logits, int unk, int rule, float* out, int ld_out, svpc_stream_t stream);
 /* ---- evaluation tail of a decode: the caption the reference submits and its repetition / diversity counts, on the device
  *      (recursive_caption_dataset.py:472-500 convert_ids_to_sentence, src/translate.py:27-42 remove_dup, densevid_eval/evaluateRepetition.py,
  *      evaluateCaptionsDiversity.py:219-282, get_caption_stat.py; the reference copies every sentence to the host, translate.py:81-82).

@@ -2687,6 +2687,64 @@ def sample_seed(src, word, used):
     return used
 
 
+ENSEMBLE_MAX = 8                # members of one ensemble: the kernel's argument struct holds their pointers by value
+ENSEMBLE_RULES = {"prob": 0, "logprob": 1}
+
+
+def ensemble_weights(weights, n):
+    """The fp64 weights of an ``n``-member ensemble, normalised to sum 1 (None: uniform; the sum is taken in member order and every
+    weight divided by it) → a list of floats.  ValueError for a wrong count, ``n`` outside 1..8, a negative or non-finite weight, and
+    weights that are all zero."""
+    if not 1 <= n <= ENSEMBLE_MAX:
+        raise ValueError("an ensemble has 1..%d members, got %d" % (ENSEMBLE_MAX, n))
+    w = [1.0] * n if weights is None else [float(v) for v in weights]
+    if len(w) != n:
+        raise ValueError("ensemble: %d weights for %d members" % (len(w), n))
+    total = 0.0
+    for v in w:
+        total += v
+    if not all(math.isfinite(v) and v >= 0 for v in w) or not (total > 0 and math.isfinite(total)):
+        raise ValueError("ensemble: weights must be finite, >= 0 and not all zero, got %r" % (w,))
+    return [v / total for v in w]
+
+
+def ensemble_combine(scores_list, row_c, *, weights, rule, logits, unk, rows_per=1, max_cols=None):
+    """The members' score matrices of one decoding step combined into ONE probability matrix (svpc_ensemble_combine):
+    ``scores_list`` M fp32 (n_rows, ≥ C) matrices with unit column stride (each its own row stride) — probabilities, or logits when
+    ``logits`` —, ``row_c`` the column counts (row r has C = row_c[r // rows_per] columns), ``weights`` M non-negative numbers (normalised
+    here; None: uniform; a zero-weight member is never read), ``rule`` "prob" (the weighted mean of the members' probabilities) or
+    "logprob" (exp of the weighted mean of their log-probabilities, not renormalised).  → out (n_rows, max_c) fp32 probabilities (0 in
+    the UNK column in logits mode and past a row's C): what the step kernels take with ``logits=False``.  The member pointers travel as
+    kernel arguments: nothing is uploaded."""
+    if rule not in ENSEMBLE_RULES:
+        raise ValueError("ensemble_combine: rule must be one of %s, got %r" % (", ".join(ENSEMBLE_RULES), rule))
+    ms = list(scores_list)
+    w = ensemble_weights(weights, len(ms))
+    for s in ms:
+        if s.dim() != 2 or s.dtype != torch.float32 or (s.stride(1) != 1 and s.shape[1] != 1):
+            raise ValueError("ensemble_combine: every member's scores must be an fp32 (rows, C) matrix with unit column stride")
+    n_rows, dev = ms[0].shape[0], ms[0].device
+    if any(s.shape[0] != n_rows or s.device != dev for s in ms):
+        raise ValueError("ensemble_combine: the members' score matrices must have the same rows on the same device")
+    if int(rows_per) < 1:
+        raise ValueError("ensemble_combine: rows_per must be >= 1")
+    rc = as_idx(row_c)
+    if len(rc) * int(rows_per) < n_rows:
+        raise ValueError("ensemble_combine: %d column counts for %d rows (%d rows each)" % (len(rc), n_rows, rows_per))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if n_rows else 1)
+    if not 1 <= max_c <= SAMPLE_COLS_MAX or any(max_c > s.shape[1] for s in ms):
+        raise ValueError("ensemble_combine: rows of 1..%d columns, inside every score matrix" % SAMPLE_COLS_MAX)
+    _need_gpu(ms[0])
+    out = torch.empty(n_rows, max_c, dtype=torch.float32, device=dev)
+    if n_rows == 0:
+        return out
+    M = len(ms)
+    _lib.call("ensemble_combine", (ctypes.c_void_p * M)(*[s.data_ptr() for s in ms]), (ctypes.c_int * M)(*[s.stride(0) for s in ms]),
+              (ctypes.c_double * M)(*w), M, _p(rc.dev(dev)), int(rows_per), n_rows, max_c, 1 if logits else 0, int(unk),
+              ENSEMBLE_RULES[rule], _p(out), out.stride(0), _stream())
+    return out
+
+
 CAPTION_LT_MAX = 64             # a caption row: one lane per position
 CAPTION_VIDEO_WORDS = 4096      # positions (S_b · Lt) of one video's captions: the words live in the workgroup's LDS
 CAPTION_COUNT_COLS = 12         # total_1..4, distinct_1..4, n_sen, n_words, n_empty, n_copied

@@ -300,6 +300,7 @@ class _DecoderSide(object):
 
     def __init__(self, model, cx, mem, bank, tab, T):
         self.model, self.cx, self.bank, self.tab, self.T = model, cx, bank, tab, T
+        self.logits = model.config.model_mode == "video"      # what ``scores`` returns: the step kernels' ``logits`` flag
         self.layers = model.decoder.layer
         self.n_mem = mem.shape[0] // T
         st = model.decoder.stacked_memory_kv()
@@ -360,7 +361,7 @@ class Translator(object):
         self.min_half = 8
         self.phase_events = None    # bench.py: a list → _decode_core (eager) appends three HIP events: start, encoder side done, end
         self._preps = {}
-        self._ttab = None
+        self._ttab = {}             # id(model) → (key, the per-checkpoint text-embedding table): see _text_table
         self._seed_word = None      # sampling with seed=None: the device-resident seed word the decode advances (see translate_batch_sample)
         self.last_sample_seed = None
         self.device = torch.device("cuda" if getattr(opt, "cuda", True) else "cpu")
@@ -816,23 +817,19 @@ class Translator(object):
         ps = [te.word_embeddings.weight] + list(te.word_fc.parameters())
         from .optim import WEIGHTS_EPOCH
         key = (tuple((p.data_ptr(), p._version) for p in ps), WEIGHTS_EPOCH[0], ops.get_precision(), Lt)
-        if self._ttab is None or self._ttab[0] != key:
+        tt = self._ttab.get(id(model))
+        if tt is None or tt[0] != key:
             V = te.word_embeddings.weight.shape[0]
             ids = torch.arange(V, dtype=torch.int32, device=dev)
             base = te.word_fc.run(te.word_embeddings.weight, cx.eps, src_rows=ids, pad_row=PAD)
-            self._ttab = (key, (base.unsqueeze(0) + te.position_embeddings_text.pe[:Lt].unsqueeze(1)).contiguous())
-        return self._ttab[1]
+            tt = self._ttab[id(model)] = (key, (base.unsqueeze(0) + te.position_embeddings_text.pe[:Lt].unsqueeze(1)).contiguous())
+        return tt[1]
 
     # ------------------------------------------------------------------ device part: encoder side once, then the decoding iterations
     def _decode_core(self, model, dp, feats, ids_all, masks_all, ingr_ids_flat):
         """→ (ids (T, K, Lt) int32, cum (T, K) fp32 or None, len (T, K) int32 or None): K = 1 (greedy, the plain beam: the chosen
         caption), B (ranked: final-key order) or R (samples in sample order)"""
-        cfg = model.config
-        mode = cfg.model_mode
-        plan, T = dp.plan, dp.T
-        dev = feats.device
-        Lt, D = cfg.max_t_len, cfg.hidden_size
-        cx = _Ctx(cfg, False, model.rng(dev))
+        cx = _Ctx(model.config, False, model.rng(feats.device))
         stamps = self.phase_events if (self.phase_events is not None and not torch.cuda.is_current_stream_capturing()) else None
 
         def stamp():
@@ -841,6 +838,42 @@ class Translator(object):
                 e.record()
                 stamps.append(e)
         stamp()
+        enc = self._encode(model, dp, feats, ids_all, masks_all, ingr_ids_flat, cx)
+        stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
+        if dp.kind == FORCE:
+            out = self._force(model, dp, enc, cx)
+        elif not self.incremental:
+            out = self._greedy_rerun(model, dp, enc[0], enc[1], cx)
+        else:
+            side = self._side(model, dp, enc, cx)
+            loop = (self._sample_iterations if dp.kind == SAMPLE else self._paragraph_iterations if dp.rounds is not None else
+                    self._beam_iterations if dp.kind == BEAM else self._greedy_iterations)
+            out = loop(dp, side)
+        stamp()
+        return out
+
+    # the three seams of ``_decode_core`` an ensemble overrides (svpc_amd/ensemble.py): what the encoder side hands on, the decoder side of
+    # the incremental loops, and forced scoring
+    def _encode(self, model, dp, feats, ids_all, masks_all, ingr_ids_flat, cx):
+        return self._encoder_side(model, dp, feats, ids_all, masks_all, ingr_ids_flat, cx)
+
+    def _side(self, model, dp, enc, cx):
+        mem, bank = enc
+        return _DecoderSide(model, cx, mem, bank, self._text_table(model, model.config.max_t_len, cx, mem.device), dp.T)
+
+    def _force(self, model, dp, enc, cx):
+        return self._force_pass(model, dp, enc[0], enc[1], cx)
+
+    def _members(self):
+        """the models a decode of this translator reads: a captured graph is valid while all of them stay where they were"""
+        return [self.model]
+
+    @staticmethod
+    def _encoder_side(model, dp, feats, ids_all, masks_all, ingr_ids_flat, cx):
+        """The encoder side of one model over the whole batch → (mem, bank): the memory rows of every sentence (n_mem per sentence) and
+        the pointer bank (None in ``video`` mode)"""
+        mode = model.config.model_mode
+        plan, T, D = dp.plan, dp.T, model.config.hidden_size
         ents = model.ingredient_embeddings.run(ingr_ids_flat, dp.spans, cx)
         cls = model._encode_clips(feats, plan.video_rows, ops.take_rows(ids_all, plan.video_rows),
                                   ops.take_rows(masks_all, plan.video_rows), plan.seq_enc, cx,
@@ -851,28 +884,11 @@ class Translator(object):
             _, _, ebar, eall, fbar = model.reasoner.run(g, ents, plan.sim, cx)
             went = ops.linear(ebar, model.Went[0].weight, model.Went[0].bias, act=ACT_RELU)
             wac = ops.linear(fbar, model.Wac[0].weight, model.Wac[0].bias, act=ACT_RELU)
-            mem = torch.stack([g, went, wac], 1).reshape(T * 3, D)
-            bank = eall
-        elif mode == "copy":
+            return torch.stack([g, went, wac], 1).reshape(T * 3, D), eall
+        if mode == "copy":
             mean_ing = ops.span_mean(ents, plan.ent_off, plan.ent_len)
-            mem = torch.stack([g, ops.take_rows(mean_ing, plan.step_vid_dev)], 1).reshape(T * 2, D)
-            bank = model._padded_bank(ents, plan)
-        else:
-            mem = g
-            bank = None
-
-        stamp()          # encoder side (clip encoder, step encoder, simulator, memory) done; the Lt decoding iterations follow
-        if dp.kind == FORCE:
-            out = self._force_pass(model, dp, mem, bank, cx)
-        elif not self.incremental:
-            out = self._greedy_rerun(model, dp, mem, bank, cx)
-        else:
-            side = _DecoderSide(model, cx, mem, bank, self._text_table(model, Lt, cx, dev), T)
-            loop = (self._sample_iterations if dp.kind == SAMPLE else self._paragraph_iterations if dp.rounds is not None else
-                    self._beam_iterations if dp.kind == BEAM else self._greedy_iterations)
-            out = loop(dp, side)
-        stamp()
-        return out
+            return torch.stack([g, ops.take_rows(mean_ing, plan.step_vid_dev)], 1).reshape(T * 2, D), model._padded_bank(ents, plan)
+        return g, None
 
     @staticmethod
     def _greedy_iterations(dp, side):
@@ -919,24 +935,39 @@ class Translator(object):
         """Forced scoring: ONE pass of the decoder side over the Lt positions of all T·K given captions (the all-positions form of
         ``_greedy_rerun``: causal ∧ pad mask, so position i sees positions 0 … i of its own caption), then ``ops.force_score`` over the
         (T·K·Lt, C) score matrix → a dict of flat device tensors (``score_captions``)."""
+        text, tmask, tgt, length, fin = Translator._force_inputs(model, dp)
+        scores = Translator._force_scores(model, dp, mem, bank, cx, text, tmask)
+        return Translator._force_finish(model, dp, scores, tgt, length, fin, model.config.model_mode == "video")
+
+    @staticmethod
+    def _force_inputs(model, dp):
+        """the given captions as the decoder takes them → (text, tmask, tgt, length, fin) (``ops.force_inputs``)"""
+        return ops.force_inputs(dp.given, model.config.vocab_size, UNK, EOS, PAD, IGNORE)
+
+    @staticmethod
+    def _force_scores(model, dp, mem, bank, cx, text, tmask):
+        """the (T·K·Lt, C) score matrix of one model over the given captions: raw logits in ``video`` mode, else the mixed probabilities"""
         cfg = model.config
-        K, T, Lt, V = dp.width, dp.T, cfg.max_t_len, cfg.vocab_size
-        text, tmask, tgt, length, fin = ops.force_inputs(dp.given, V, UNK, EOS, PAD, IGNORE)
+        Lt = cfg.max_t_len
         xt = model.text_embeddings.run(text.reshape(-1), Lt, cx)
         dec = model.decoder.run(xt, tmask.reshape(-1), mem, dp.force_self, dp.force_cross, None, cx)
         logits = model.decoder_classifier.run(dec, cx.eps)
         if cfg.model_mode == "video":
-            scores = logits                                   # raw logits: the step score is their log_softmax (translator.py:159)
-        else:
-            pl = dp.ptr_force
-            pi = g = None
-            if bank is not None:        # the K captions of a sentence read its bank: one launch per k, nothing replicated
-                pi, g = ops.ptr_attn_gate_groups(dec, model.bank_projection(bank), bank, pl["step_ne"], Lt, dp.group_rows,
-                                                 model.pgen_linear[0].weight, model.pgen_linear[0].bias)
-            labels = torch.full((dec.shape[0],), -1, dtype=torch.int32, device=dec.device)
-            scores = ops.ptr_mix_loss(logits, g, pi, labels, pl["row_c"], pl["row_vid"], pl["csr_off"], pl["csr_ent"], pl["csr_id"],
-                                      pl["csr_w"], pl["c_max"], model.label_smoothing)[0]
-        r = ops.force_score(scores, dp.cap_c, tgt, length, cfg.model_mode == "video", UNK, dp.unk, max_cols=max(dp.c_list))
+            return logits                                     # raw logits: the step score is their log_softmax (translator.py:159)
+        pl = dp.ptr_force
+        pi = g = None
+        if bank is not None:        # the K captions of a sentence read its bank: one launch per k, nothing replicated
+            pi, g = ops.ptr_attn_gate_groups(dec, model.bank_projection(bank), bank, pl["step_ne"], Lt, dp.group_rows,
+                                             model.pgen_linear[0].weight, model.pgen_linear[0].bias)
+        labels = torch.full((dec.shape[0],), -1, dtype=torch.int32, device=dec.device)
+        return ops.ptr_mix_loss(logits, g, pi, labels, pl["row_c"], pl["row_vid"], pl["csr_off"], pl["csr_ent"], pl["csr_id"],
+                                pl["csr_w"], pl["c_max"], model.label_smoothing)[0]
+
+    @staticmethod
+    def _force_finish(model, dp, scores, tgt, length, fin, logits):
+        """``ops.force_score`` over a (T·K·Lt, C) score matrix (logits when ``logits``) → the dict ``score_captions`` splits"""
+        K, T, Lt = dp.width, dp.T, model.config.max_t_len
+        r = ops.force_score(scores, dp.cap_c, tgt, length, logits, UNK, dp.unk, max_cols=max(dp.c_list))
         return dict(cum=r["cum"].view(T, K), length=length.view(T, K), finished=fin.view(T, K), n_scored=r["n_scored"].view(T, K),
                     step=r["step"].view(T, K, Lt - 1), rank=r["rank"].view(T, K, Lt - 1), top=r["top"].view(T, K, Lt - 1),
                     top_step=r["top_step"].view(T, K, Lt - 1))
@@ -1000,16 +1031,16 @@ class Translator(object):
             t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
             scores = side.scores(rows, ptr, nxt, i, caches, seq_self[i], seq_cross, t_in[2], B)
             if phi is not None:
-                _, _, nxt = ops.stochastic_beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, phi, gk,
+                _, _, nxt = ops.stochastic_beam_step(scores, ptr["row_c"], row_x, B, i, side.logits, UNK, EOS, PAD, cum, phi, gk,
                                                      fin, length, t_in, t_out, Lt, dp.seed_used, **dp.stochastic)
             elif cstate is not None:
-                _, _, nxt = ops.beam_step_cons(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, cstate, fin,
+                _, _, nxt = ops.beam_step_cons(scores, ptr["row_c"], row_x, B, i, side.logits, UNK, EOS, PAD, cum, cstate, fin,
                                                length, t_in, t_out, Lt, dp.cons, **dp.controls)
             elif G is None:
-                _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
+                _, _, nxt = ops.beam_step(scores, ptr["row_c"], row_x, B, i, side.logits, UNK, EOS, PAD, cum, fin, t_in, t_out, Lt,
                                           **ctl)
             else:
-                _, _, nxt = ops.beam_step_groups(scores, ptr["row_c"], row_x, B, G, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, aug, fin,
+                _, _, nxt = ops.beam_step_groups(scores, ptr["row_c"], row_x, B, G, i, side.logits, UNK, EOS, PAD, cum, aug, fin,
                                                  length, t_in, t_out, Lt, dp.pen, **dp.controls)
         ext = toks[(Lt - 1) % 2][1]
         if phi is not None:      # no final re-ranking: selection order is descending G, the order drawn
@@ -1063,7 +1094,7 @@ class Translator(object):
         caches, rows, seq_self, seq_cross = side.caches(n), side.rows(), self._self_segs(dp, Lt, dev), side.seq_cross(dp)
         for i in range(Lt - 1):
             scores = side.scores(rows, dp.ptr_hyp, nxt, i, caches, seq_self[i], seq_cross, dp.key_rows, R)
-            _, nxt = ops.sample_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, cfg.model_mode == "video", UNK, EOS, PAD, cum, fin, length,
+            _, nxt = ops.sample_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, side.logits, UNK, EOS, PAD, cum, fin, length,
                                      text, ext, dp.seed_used, **dp.sampling)
         return ext.view(T, R, Lt), cum.view(T, R), length.view(T, R)
 
@@ -1197,14 +1228,15 @@ class Translator(object):
         from .optim import WEIGHTS_EPOCH
         # (epoch + the embedding parameters' version counters: the graph holds the address of the per-checkpoint text-embedding table,
         # which ``_text_table`` rebuilds — elsewhere — when either moves: load_state_dict / copy_ into the same tensors bump only the versions)
-        te = model.text_embeddings
         S_pad, n, L, F = shape
         from .graph import ops_stream
         cur = torch.cuda.current_stream()
         side = stream if stream is not None else (cur if cur != torch.cuda.default_stream() else ops_stream())
-        sig = (tuple(p.data_ptr() for p in list(model.parameters())[:8]), _ops.get_precision(),
-               id(getattr(model, "_svpc_weight_store", None)), WEIGHTS_EPOCH[0],
-               tuple(p._version for p in [te.word_embeddings.weight] + list(te.word_fc.parameters())), side.cuda_stream)
+        mods = self._members()           # (every model the decode reads: an ensemble's graph holds all its members' addresses)
+        sig = (tuple(p.data_ptr() for m in mods for p in list(m.parameters())[:8]), _ops.get_precision(),
+               tuple(id(getattr(m, "_svpc_weight_store", None)) for m in mods), WEIGHTS_EPOCH[0],
+               tuple(p._version for m in mods for p in [m.text_embeddings.word_embeddings.weight] + list(m.text_embeddings.word_fc.parameters())),
+               side.cuda_stream)
         gkey = side.cuda_stream                      # one graph per replay stream: two halves of ONE structure must not share captured buffers
         g = dp.graphs.get(gkey)
         if g is not None and g[3] != sig:
