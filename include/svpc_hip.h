@@ -764,6 +764,26 @@ int svpc_seq_ul_bwd(const float* scores, int ld, const int* row_c, int max_c, co
                     const int* neg, int m, const float* row_w, const float* row_u, const float* dl, int n_cap, int lt, int logits, int unk,
                     float* dscores, int ld_out, svpc_stream_t stream);
 
+/* ---- knowledge distillation against a teacher's per-position distribution.  Layout, tgt / len as the sequence
+ *      log-likelihood above.  scores (ld floats per row; logits != 0: raw logits) is the student's matrix, tq (ldq floats per row;
+ *      teacher_logits != 0: raw logits) the teacher's over the same rows; max_c <= ld, ldq.  Over the candidates (c < row_c[r], c != unk),
+ *      in fp64: q_c = raw > 0 ? raw : 0, or exp(raw − the teacher row's log-sum-exp without unk) (0 everywhere when that is not finite),
+ *      never renormalised; l_c = log p_c, or raw − the student row's log-sum-exp; a column with q_c > 0 is clamped when p_c <= 0 or
+ *      l_c < log 2^-100: its term is −q_c·log 2^-100 and its gradient 0. */
+/* step / cum / barred as svpc_seq_nll_fwd (the same bits); kdstep (n_cap, lt − 1) = fp32(−sum q_c·l_c), hstep = fp32(−sum q_c·log q_c) over
+ * the candidates with q_c > 0 (0 past the end), per lane the columns lane, lane + 64, … then the butterfly; kd / ent (n_cap,) their fp32
+ * running sums in position order; loss (1,) = fp32(−sum row_w·cum + sum row_v·kd) over the captions not barred, products and sums in fp64
+ * in svpc_seq_nll_fwd's order (row_v all 0: its bits).  Three launches. */
+int svpc_seq_kd_fwd(const float* scores, int ld, const float* tq, int ldq, const int* row_c, int max_c, const int* tgt, const int* len,
+                    const float* row_w, const float* row_v, int n_cap, int lt, int logits, int teacher_logits, int unk, float* step,
+                    float* kdstep, float* hstep, float* cum, float* kd, float* ent, int* barred, float* loss, svpc_stream_t stream);
+/* dscores as svpc_seq_nll_bwd, every element written, with the distillation term's gradient on the rows that are not zero: probabilities,
+ * −dl·row_v[r]·q_c / p_c added at every unclamped column with q_c > 0; logits, dl·row_v[r]·(Q'·p_c − q'_c) added at every candidate column,
+ * q' = q on the unclamped columns, Q' = sum q'.  The teacher gets no gradient.  A row with dl·row_v[r] = 0 has svpc_seq_nll_bwd's bits. */
+int svpc_seq_kd_bwd(const float* scores, int ld, const float* tq, int ldq, const int* row_c, int max_c, const int* tgt, const int* len,
+                    const int* barred, const float* row_w, const float* row_v, const float* dl, int n_cap, int lt, int logits,
+                    int teacher_logits, int unk, float* dscores, int ld_out, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

@@ -119,4 +119,6 @@ class EnsembleTranslator(Translator):
         mats = [self._force_scores(m, dp, mem, bank, cxm, text, tmask) for m, cxm, mem, bank in enc]
         scores = ops.ensemble_combine(mats, dp.cap_c, weights=self.weights, rule=self.combine, logits=model.config.model_mode == "video",
                                       unk=UNK, rows_per=model.config.max_t_len, max_cols=max(dp.c_list))
+        if dp.raw:                                 # ``teacher_scores``: the combined matrix itself, probabilities in every mode
+            return self._force_raw(model, dp, scores, False)
         return self._force_finish(model, dp, scores, tgt, length, fin, False)

@@ -3490,3 +3490,103 @@ def seq_ul(scores, row_c, tgt, length, neg, row_w, row_u, logits, unk_id, max_co
     check_unlikelihood(lt=lt, neg=neg, rows=R, device=scores.device, row_w=row_w, row_u=row_u)
     _need_gpu(scores)
     return _SeqUl.apply(_c(scores), rc.dev(scores.device), tgt, length, neg, row_w, row_u, 1 if logits else 0, int(unk_id), max_c)
+
+
+# ------------------------------------------------------------------------------------------------ knowledge distillation
+KD_LOG_EPS = -100.0 * math.log(2.0)     # log ε, ε = 2^-100: the clamp on the student's log-probability (svpc_seq_kd_fwd)
+
+
+def check_distill(alpha=None, tq=None, tq_rows=None, max_cols=None, device=None, row_w=None, row_v=None, rows=None, weights=None,
+                  kd_weights=None, shape=None, need_gpu=True):
+    """Host checks of knowledge distillation (ValueError for each): ``alpha`` a finite number in [0, 1]; ``tq`` an fp32
+    matrix of ``tq_rows`` rows (the student's row count) and at least ``max_cols`` columns, unit column stride, rows that do not overlap, on
+    ``device``; ``row_w`` / ``row_v`` contiguous fp32 (``rows``,) on ``device``; ``weights`` / ``kd_weights`` floating point of ``shape``
+    (T, K) or (T·K,).  ``SvpcKernelError`` for a tensor that is not on the GPU (no CPU fallback exists), unless ``need_gpu`` is off (a
+    caller whose other checks come first)."""
+    if alpha is not None and (isinstance(alpha, bool) or not isinstance(alpha, numbers.Real) or not math.isfinite(alpha)
+                              or not 0.0 <= alpha <= 1.0):
+        raise ValueError("alpha must be a finite number in [0, 1], got %r" % (alpha,))
+    if tq is not None:
+        if not torch.is_tensor(tq) or tq.dim() != 2 or tq.dtype != torch.float32:
+            raise ValueError("tq, the teacher's score matrix, must be an fp32 (rows, columns) tensor, got %s"
+                             % ("%s %s" % (tuple(tq.shape), tq.dtype) if torch.is_tensor(tq) else type(tq).__name__))
+        if device is not None and tq.device != device:
+            raise ValueError("tq must be on the scores' device %s, got %s" % (device, tq.device))
+        if tq_rows is not None and tq.shape[0] != tq_rows:
+            raise ValueError("tq must have the student's %d score rows, got %d" % (tq_rows, tq.shape[0]))
+        if max_cols is not None and tq.shape[1] < max_cols:
+            raise ValueError("tq is narrower (%d columns) than max_cols = %d" % (tq.shape[1], max_cols))
+        if (tq.shape[1] and tq.stride(1) != 1) or (tq.shape[0] > 1 and tq.stride(0) < (max_cols or tq.shape[1])):
+            raise ValueError("tq must have unit column stride and rows that do not overlap, got strides %s" % (tuple(tq.stride()),))
+    for name, t in (("row_w", row_w), ("row_v", row_v)):
+        if t is not None and (not torch.is_tensor(t) or not _row_vec(t, rows, torch.float32, device)):
+            raise ValueError("%s must be contiguous fp32 (%s,) on the scores' device" % (name, rows))
+    for name, t in (("weights", weights), ("kd_weights", kd_weights)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_floating_point()
+                              or tuple(t.shape) not in (tuple(shape), (shape[0] * shape[1],))):
+            raise ValueError("%s must be floating point %s or (%d,), got %s"
+                             % (name, tuple(shape), shape[0] * shape[1], tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    for t in (tq, row_w, row_v, weights, kd_weights):
+        if need_gpu and t is not None and not t.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.ops: knowledge distillation runs on the GPU only (no CPU fallback exists)")
+
+
+class _SeqKd(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, tq, row_w, row_v, logits, teacher_logits, unk_id, max_c):
+        R, lt = tgt.shape
+        dev = scores.device
+        step, kdstep, hstep = (torch.empty(R, lt - 1, dtype=torch.float32, device=dev) for _ in range(3))
+        cum, kd, ent = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_kd_fwd", _p(scores), scores.stride(0), _p(tq), tq.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(row_w), _p(row_v),
+                  R, lt, logits, teacher_logits, unk_id, _p(step), _p(kdstep), _p(hstep), _p(cum), _p(kd), _p(ent), _p(barred), _p(loss),
+                  _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, tq, row_w, row_v)
+        ctx.cfg = (R, lt, logits, teacher_logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred, kd, kdstep, ent, hstep)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred, kd, kdstep, ent, hstep
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 11
+        scores, rc, tgt, length, barred, tq, row_w, row_v = ctx.saved_tensors
+        R, lt, logits, teacher_logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        _lib.call("seq_kd_bwd", _p(scores), scores.stride(0), _p(tq), tq.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(row_w),
+                  _p(row_v), _p(dl), R, lt, logits, teacher_logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return (dscores,) + (None,) * 10
+
+
+def seq_kd(scores, row_c, tgt, length, tq, row_w, row_v, logits, teacher_logits, unk_id, max_cols=None):
+    """``seq_nll`` plus the distillation term against a teacher's score matrix (svpc_seq_kd_fwd / _bwd), differentiable in
+    ``scores`` only: ``tq`` (R·Lt, ≥ max_cols) fp32 — the teacher's scores of the same rows, any row stride; probabilities, or raw logits when
+    ``teacher_logits`` —, ``row_v`` (R,) fp32 the captions' distillation weights, the rest as ``seq_nll`` takes it → (loss () fp32 =
+    −Σ w_r·cum_r + Σ v_r·kd_r over the captions that are not barred, cum, step, barred as ``seq_nll`` returns them — the same bits —, kd
+    (R,) fp32, kdstep (R, Lt − 1) fp32: the cross-entropy −Σ_c q_c·log p_c of the position's student row against its teacher row over
+    the candidates, a log-probability under log 2^-100 clamped there with a zero gradient; ent (R,) / hstep (R, Lt − 1) fp32: the
+    teacher's entropy −Σ_c q_c·log q_c, so kd − ent is the KL divergence of a teacher that sums to 1).  The teacher is not renormalised
+    and gets no gradient.  With ``row_v`` all zero the loss and its gradient have ``seq_nll``'s bits."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_kd: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_kd: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_kd: length must be contiguous int32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_kd: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_kd: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    check_distill(tq=tq, tq_rows=scores.shape[0], max_cols=max_c, device=scores.device, row_w=row_w, row_v=row_v, rows=R)
+    _need_gpu(scores)
+    return _SeqKd.apply(_c(scores), rc.dev(scores.device), tgt, length, tq.detach(), row_w, row_v, 1 if logits else 0,
+                        1 if teacher_logits else 0, int(unk_id), max_c)

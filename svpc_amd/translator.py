@@ -283,6 +283,7 @@ class DecodePlan(object):
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
                  "stochastic",                                  # stochastic beam search: ops.stochastic_beam_step's keywords (+ the seed words)
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
+                 "raw",                                         # forced pass stopped at the score matrix (``teacher_scores``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
                  "graphs")                                      # replay stream → (graph, captured inputs, outputs, signature)
 
@@ -645,6 +646,23 @@ class Translator(object):
             ("step_list", "step"), ("rank_list", "rank"), ("top_list", "top"), ("top_step_list", "top_step"))}
         return SimpleNamespace(**lists, **r)
 
+    @torch.no_grad()
+    def teacher_scores(self, model_inputs, dec_seq_list):
+        """The forced pass of ``score_captions`` stopped before ``ops.force_score``: this translator's per-position distribution over GIVEN
+        captions, the teacher's side of knowledge distillation (``svpc_amd.distill``).  ``model_inputs`` and
+        ``dec_seq_list`` as ``score_captions`` takes them — the same checks, the same in-place blanking of the text half of the ids /
+        masks.  → a namespace: ``scores`` (T·K·Lt, ld) fp32 — row (t·K + k)·Lt + i scores position i + 1 of caption k of sentence t; raw
+        logits when ``logits`` (a single ``video``-mode model), else probabilities (an ensemble's combined matrix always) —, ``logits``,
+        ``cap_c`` the T·K caption rows' column counts (an Idx), ``max_cols``, ``T``, ``K``, ``Lt``.  With ``graph=True`` this pass still
+        runs EAGER: the matrix is a fresh tensor the caller owns, never a captured buffer, so it stays valid for as long as it is
+        referenced (``score_captions`` keeps its graph).  No host synchronisation."""
+        ids, steps = ops.stack_captions(dec_seq_list)
+        if steps != [int(s) for s in model_inputs[11]]:
+            raise ValueError("teacher_scores: the captions' rows per video %r are not the batch's step counts %r" % (steps, list(model_inputs[11])))
+        _, K, _, _ = ops.check_force(ids, self.max_t_len, steps, "bar")
+        decode = Decode(FORCE, K, sampling=("bar", ids.dtype, "raw"), given=ids)
+        return SimpleNamespace(**self._translate(model_inputs, self.model, decode=decode))
+
     def gold_captions(self, input_labels_list, batch_step_num):
         """The reference captions of a batch as a ``dec_seq_list`` for ``score_captions``, on the device: ``input_labels_list`` the
         per-step (N, Lv + Lt) label tensors of the training batch (the label at text position j is the word at caption position
@@ -762,7 +780,8 @@ class Translator(object):
         their own, which a captured graph reads."""
         plan, T, K, Lt = dp.plan, dp.T, dp.width, model.config.max_t_len
         n_mem, R = model._n_mem(), dp.T * dp.width
-        dp.unk, id_dtype = decode.sampling
+        dp.unk, id_dtype = decode.sampling[:2]
+        dp.raw = len(decode.sampling) > 2          # (``teacher_scores``: a third entry of the setting, so a plan of its own)
         dp.given = torch.empty(T, K, Lt, dtype=id_dtype, device=dev)
         dp.cap_c = Idx([c_list[b] for b in plan.step_vid.host for _ in range(K)])
         dp.ptr_force = model._ptr_plan(dicts, c_list, K * Lt, plan.step_ne, Idx([b for b in plan.step_vid.host for _ in range(K * Lt)]))
@@ -862,7 +881,17 @@ class Translator(object):
         return _DecoderSide(model, cx, mem, bank, self._text_table(model, model.config.max_t_len, cx, mem.device), dp.T)
 
     def _force(self, model, dp, enc, cx):
+        if dp.raw:                                 # ``teacher_scores``: the forced pass stopped before ``_force_finish``
+            text, tmask, _tgt, _len, _fin = self._force_inputs(model, dp)
+            scores = self._force_scores(model, dp, enc[0], enc[1], cx, text, tmask)
+            return self._force_raw(model, dp, scores, model.config.model_mode == "video")
         return self._force_pass(model, dp, enc[0], enc[1], cx)
+
+    @staticmethod
+    def _force_raw(model, dp, scores, logits):
+        """what ``teacher_scores`` returns of a (T·K·Lt, C) score matrix (logits when ``logits``)"""
+        return dict(scores=scores, logits=bool(logits), cap_c=dp.cap_c, max_cols=max(dp.c_list), T=dp.T, K=dp.width,
+                    Lt=model.config.max_t_len)
 
     def _members(self):
         """the models a decode of this translator reads: a captured graph is valid while all of them stay where they were"""
@@ -1153,7 +1182,7 @@ class Translator(object):
             if dp.cons is not None:           # the constraint table: one host-to-device copy per call
                 dp.cons.copy_(decode.cons)
             src = (feats4[:, lo:hi], ids3[:, lo:hi], masks3[:, lo:hi], ingr_all[lo:hi])
-            if not self.graph or dev.type != "cuda":
+            if not self.graph or dev.type != "cuda" or dp.raw:       # (``teacher_scores`` runs eager: its matrix is the caller's)
                 out = self._decode_core(model, dp, src[0].reshape(S_pad * n * L, F), src[1].reshape(-1).to(torch.int32),
                                         src[2].reshape(-1).float(), src[3].reshape(-1))
             else:
