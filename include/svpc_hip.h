@@ -578,6 +578,26 @@ int svpc_beam_step_gumbel(const float* scores, int ld, const int* row_c, const i
                           const int* rows_in, int* text_out, int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext,
                           int* next_model, double temp, int min_len, const long long* seed, double* phi, double* gkey, int* len, int max_c,
                           svpc_stream_t stream);
+/* contrastive search (Su et al. 2022; HuggingFace generate(penalty_alpha, top_k)): svpc_beam_step's launch shape, score rows and ping-pong
+ * tables over `k` candidate rows per sentence, with the state per SENTENCE: ids / pen ((n_sent, ld_tok): the committed extended ids and the
+ * winners' penalties), cum (fp32), len, finished ((n_sent,)), hist ((n_sent, ld_tok, d) fp32: the committed positions' hidden states) and
+ * hist_n2 ((n_sent, ld_tok) fp64: their squared norms).  Called AFTER the decoder pass at position pos, whose row r = t·k + h carries one
+ * candidate word for position pos (extended id ext_in[r][pos]) with cand_p[r] (its probability; 0: dead) and cand_score[r] (its step score),
+ * and whose last-layer output is hidden[r] (d floats, row stride ld_h).  penalty_r = max over j < pos of cos(hidden[r], hist[t][j]) (fp64
+ * dots and norms in a fixed order; 0 at pos 0 and when a norm is 0); score_r = (1 − alpha)·p_r − alpha·penalty_r; the winner is the live row
+ * with the highest score, ties to the lowest row → winner[t] (−1: none).  Commit: ids[t][pos] = its id, cum[t] += its step score, len[t] =
+ * pos, pen[t][pos], hist[t][pos] and hist_n2[t][pos]; eos finishes the sentence.  Expansion (pos + 1 < ld_tok, not finished): the top k
+ * columns c < row_c <= max_c <= 4096 of the winner's score row by higher raw value, then lower column, without unk and without eos while
+ * pos + 1 <= min_len, become the k rows' candidates at pos + 1: p the raw value (<= 0: 0), in logits mode fp32(exp(raw − lse)); a column
+ * with p = 0 or a missing one is dead (pad, p 0, step score −inf); every child takes the winner's token and ancestry rows for positions <=
+ * pos and its own cache slot at pos + 1, out as svpc_beam_step's.  A finished sentence writes pad children and nothing else; a sentence
+ * without a live row finishes with pad and cum = −inf.  scores may be NULL at pos + 1 == ld_tok (no expansion).  Everything travels by
+ * value: graph-capture safe. */
+int svpc_contrastive_step(const float* scores, int ld, const int* row_c, const int* row_x, int n_sent, int k, int pos, int logits, int unk,
+                          int eos, int pad, int slot_rows, const float* hidden, int ld_h, int d, double alpha, int min_len, int max_c,
+                          float* cand_p, float* cand_score, const int* text_in, const int* ext_in, const int* rows_in, int* text_out,
+                          int* ext_out, int* rows_out, int ld_tok, int* parent, int* next_ext, int* next_model, int* ids, float* cum,
+                          int* len, float* pen, int* finished, float* hist, double* hist_n2, int* winner, svpc_stream_t stream);
 /* random-sampling decoding step (the random-sampling strategy of the reference's OpenNMT decode-strategy lineage: random_sampling_temp,
  * random_sampling_topk, random_sampling_topp): one wave per sample row r of `scores` (n_rows rows; row r: its first row_c[r] <= max_c <= 4096
  * columns, the last row_x[r] of them copied OOV words).  Step scores as svpc_beam_step's (logits == 0: log p; logits != 0: logit − the

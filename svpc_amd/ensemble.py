@@ -96,6 +96,10 @@ class EnsembleTranslator(Translator):
         if on:
             raise ValueError("an ensemble decodes on one stream: two_streams is not offered")
 
+    def translate_batch_contrastive(self, model_inputs, top_k=None, penalty_alpha=None, min_length=None, **unknown):
+        raise NotImplementedError("contrastive search is not offered for an ensemble: the degeneration penalty compares hidden states, and "
+                                  "M members have M hidden spaces (the combined score rows have none)")
+
     def _members(self):
         return self.models
 

@@ -2479,6 +2479,86 @@ def stochastic_beam_step(scores, row_c, row_x, beam, pos, logits, unk, eos, pad,
     return outs
 
 
+def check_contrastive(lt, top_k, penalty_alpha, min_length=0, max_cols=None):
+    """The settings of a contrastive search (Su et al. 2022) over Lt = ``lt`` positions, checked on the host (ValueError) and normalised →
+    dict(top_k k (an integer 1 … BEAM_MAX), penalty_alpha α (a finite number in [0, 1], rounded to fp32: the value the kernel and a
+    captured graph hold), min_length m (0 … Lt − 1)).  ``max_cols``: the widest score row C_r = V + X of the batch (≤ SAMPLE_COLS_MAX)."""
+    k = _as_int("top_k", top_k)
+    if not 1 <= k <= BEAM_MAX:
+        raise ValueError("top_k must be 1..%d, got %d" % (BEAM_MAX, k))
+    if isinstance(penalty_alpha, bool) or not isinstance(penalty_alpha, numbers.Real):
+        raise ValueError("penalty_alpha must be a number, got %r" % (penalty_alpha,))
+    alpha = float(penalty_alpha)
+    if not math.isfinite(alpha) or not 0.0 <= alpha <= 1.0:
+        raise ValueError("penalty_alpha must be a finite number in [0, 1], got %r" % (penalty_alpha,))
+    m = _as_int("min_length", min_length)
+    if not 0 <= m <= lt - 1:
+        raise ValueError("min_length must be 0..%d (Lt - 1), got %d" % (lt - 1, m))
+    if max_cols is not None and int(max_cols) > SAMPLE_COLS_MAX:
+        raise ValueError("contrastive search reads score rows of at most %d columns (vocabulary + copied words), got %d"
+                         % (SAMPLE_COLS_MAX, max_cols))
+    return dict(top_k=k, penalty_alpha=struct.unpack("f", struct.pack("f", alpha))[0], min_length=m)
+
+
+def contrastive_step(scores, row_c, row_x, top_k, pos, logits, unk, eos, pad, hidden, cand_p, cand_score, ids, cum, length, pen, finished,
+                     hist, hist_n2, toks_in, toks_out, slot_rows, *, alpha, min_length=0, max_cols=None):
+    """One selection step of contrastive search (svpc_contrastive_step) after the decoder pass at position ``pos`` over ``top_k`` candidate
+    rows per sentence: ``hidden`` (T·k, D) fp32 is the pass's last-layer output, ``scores`` (T·k, ≥ C) its score rows (``beam_step``'s; None
+    at the last position pos = Lt − 1, which has no expansion).  In place, all contiguous on the hidden rows' device — per row (T·k,):
+    ``cand_p`` / ``cand_score`` fp32, the probability (0: a dead candidate) and the step score of the word the row carries, replaced by
+    the children's; per sentence: ``ids`` (T, Lt) int32 committed extended ids, ``cum`` (T,) fp32, ``length`` (T,) int32, ``pen`` (T, Lt)
+    fp32 the winners' penalties, ``finished`` (T,) int32, ``hist`` (T, Lt, D) fp32 the committed positions' hidden states and ``hist_n2``
+    (T, Lt) float64 their squared norms.  ``toks_in`` / ``toks_out`` as ``beam_step``'s (the k children descend from the winner).
+    ``alpha`` the degeneration penalty's weight in [0, 1]; EOS is barred while pos + 1 ≤ ``min_length``; ``max_cols``: max(row_c) when the
+    caller knows it.  → (winner (T,) int32: the winning row of each sentence, −1 for none; parent, next_ext, next_model (T·k,) int32)."""
+    k = top_k
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= k <= BEAM_MAX:
+        raise ValueError("contrastive_step: top_k must be 1..%d" % BEAM_MAX)
+    dev = hidden.device
+    if hidden.dim() != 2 or hidden.dtype != torch.float32 or hidden.stride(1) != 1 or hidden.shape[0] % k or hidden.shape[1] < 1:
+        raise ValueError("contrastive_step: hidden must be fp32 (T·k, D) rows with unit column stride")
+    R, D = hidden.shape
+    T = R // k
+    lt = toks_in[0].shape[1]
+    if not 0 <= pos < lt or slot_rows < lt:
+        raise ValueError("contrastive_step: position %d outside the %d-column tables" % (pos, lt))
+    if scores is None:
+        if pos != lt - 1:
+            raise ValueError("contrastive_step: only the last position runs without score rows")
+    elif scores.dim() != 2 or scores.shape[0] != R or scores.stride(1) != 1 or scores.dtype != torch.float32 or scores.device != dev:
+        raise ValueError("contrastive_step: scores must be fp32 (T·k, C) rows with unit column stride on the hidden rows' device")
+    if not (_row_vec(cand_p, R, torch.float32, dev) and _row_vec(cand_score, R, torch.float32, dev)):
+        raise ValueError("contrastive_step: cand_p and cand_score fp32, contiguous (T·k,) on the hidden rows' device")
+    if not (_row_vec(cum, T, torch.float32, dev) and _row_vec(length, T, torch.int32, dev) and _row_vec(finished, T, torch.int32, dev)
+            and _id_rows(ids, T, lt, dev) and pen.dtype == torch.float32 and tuple(pen.shape) == (T, lt) and pen.is_contiguous()
+            and pen.device == dev):
+        raise ValueError("contrastive_step: cum fp32, length and finished int32 (T,), ids int32 and pen fp32 (T, Lt), all contiguous on "
+                         "the hidden rows' device")
+    if not (hist.dtype == torch.float32 and tuple(hist.shape) == (T, lt, D) and hist.is_contiguous() and hist.device == dev
+            and hist_n2.dtype == torch.float64 and tuple(hist_n2.shape) == (T, lt) and hist_n2.is_contiguous() and hist_n2.device == dev):
+        raise ValueError("contrastive_step: hist fp32 (T, Lt, D) and hist_n2 float64 (T, Lt), contiguous on the hidden rows' device")
+    for m in tuple(toks_in) + tuple(toks_out):
+        if not _id_rows(m, R, lt, dev):
+            raise ValueError("contrastive_step: token / ancestry tables must be contiguous int32 (T·k, Lt) on the hidden rows' device")
+    if any(i.data_ptr() == o.data_ptr() for i, o in zip(toks_in, toks_out)):
+        raise ValueError("contrastive_step: the token and ancestry tables are ping-pong pairs")
+    a = float(alpha)
+    if not (math.isfinite(a) and 0.0 <= a <= 1.0 and 0 <= int(min_length) < lt):
+        raise ValueError("contrastive_step: alpha a finite number in [0, 1], min_length 0..Lt-1")
+    max_c = int(max_cols) if max_cols is not None else (max(as_idx(row_c).host) if R else 1)
+    if max_c > SAMPLE_COLS_MAX or max_c < 1 or (scores is not None and max_c > scores.shape[1]):
+        raise ValueError("contrastive_step: rows of 1..%d columns, inside the score matrix" % SAMPLE_COLS_MAX)
+    _need_gpu(hidden)
+    winner = torch.empty(T, dtype=torch.int32, device=dev)
+    outs = tuple(torch.empty(R, dtype=torch.int32, device=dev) for _ in range(3))
+    _lib.call("contrastive_step", _p(scores), scores.stride(0) if scores is not None else max_c, _p(as_idx(row_c).dev(dev)),
+              _p(as_idx(row_x).dev(dev)), T, int(k), int(pos), 1 if logits else 0, int(unk), int(eos), int(pad), int(slot_rows), _p(hidden),
+              hidden.stride(0), D, a, int(min_length), max_c, _p(cand_p), _p(cand_score), _p(toks_in[0]), _p(toks_in[1]), _p(toks_in[2]),
+              _p(toks_out[0]), _p(toks_out[1]), _p(toks_out[2]), lt, _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(ids), _p(cum), _p(length),
+              _p(pen), _p(finished), _p(hist), _p(hist_n2), _p(winner), _stream())
+    return (winner,) + outs
+
+
 CONS_MAX = 4                    # constraints (phrases) of a sentence
 CONS_LEN = 4                    # extended ids of a phrase
 

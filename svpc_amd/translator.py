@@ -184,6 +184,32 @@ drawn.  Restated by tests/stochastic_beam_reference.py:
   ``random_sampling_topp`` included); ``incremental=False`` raises NotImplementedError.  Each setting (W, τ, m) has its own plan and
   captured graph; ``translate_batch_consensus(source="stochastic", num_candidates=K)`` decodes with W = K.
 
+**Contrastive search** (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; HuggingFace's ``generate(penalty_alpha,
+top_k)``): ``translate_batch_contrastive(model_inputs, top_k=None, penalty_alpha=None, min_length=None)`` →
+``(dec_seq_list, oov_word_dict, score_list, length_list, penalty_list)``: per video ids (S_b, Lt) int64, cum (S_b,) fp32, len (S_b,) int64
+and pen (S_b, Lt) fp32 — one caption per sentence, deterministic, a soft repetition penalty taken from the model's own representation.
+Restated by tests/contrastive_reference.py:
+
+- a sentence has k = ``top_k`` candidate rows (1 ≤ k ≤ 8) and α = ``penalty_alpha`` ∈ [0, 1] (rounded to fp32); the loop runs Lt decoder
+  passes, one more than the other loops: a word is chosen by its own hidden state, so the word at position Lt − 1 needs a pass too (that
+  pass runs without the head);
+- pass 0: every row carries BOS, row 0 alone is live and wins; its last-layer output is history entry 0;
+- pass i ≥ 1: row r carries a candidate word for position i with p_r (the model's probability of it given positions 0 … i − 1) and s_r
+  (its step score, beam's); h_r is the row's last-layer output (the matrix the head reads, as fp32); penalty_r = max over j < i of
+  cos(h_r, H[j]); score_r = (1 − α)·p_r − α·penalty_r; the live row with the highest score wins, ties to the lowest row; its id, fp32(cum +
+  s), len = i, its penalty and its hidden state are committed; EOS finishes the sentence;
+- expansion (i < Lt − 1, not finished): the top k columns of the winner's score row by higher raw value, then lower column, without UNK,
+  without EOS while i + 1 ≤ ``min_length`` (skipped, nothing renormalised) become the k rows' candidates at i + 1; p is the raw value (≤ 0:
+  0), in ``video`` mode fp32(exp(raw − lse)); a candidate with p = 0 is dead (PAD, never wins); all k children take the winner's token
+  rows and KV ancestry;
+- dot products, norms, cosines and scores are fp64 (cos is 0 when a norm is 0); a finished sentence writes PAD; a sentence without a live
+  candidate finishes with PAD and cum = −inf;
+- the candidate rows are in descending-p order, so α = 0 (any k) and k = 1 (any α) give the width-1 beam's ids and cum; len counts as
+  ``translate_batch_nbest``'s; pen is 0 at position 0 and after the end;
+- defaults ``opt.top_k`` (4), ``opt.penalty_alpha`` (0.6), ``opt.min_length`` (0); ValueError on the host for k, α, m and rows wider
+  than 4096 columns; TypeError for any other keyword; ``incremental=False`` raises NotImplementedError, and so does an
+  ``EnsembleTranslator`` (M members have M hidden spaces).  Each setting (k, α, m) has its own plan and captured graph.
+
 **Forced scoring** (the GOLD score / gold perplexity of the reference decoder's OpenNMT lineage):
 ``Translator.score_captions(model_inputs, dec_seq_list, unk="bar")`` scores GIVEN captions under decoding conditions (text half masked,
 ``log p`` of the mixed pointer-generator distribution).  The definition, restated by tests/forced_score_reference.py:
@@ -245,14 +271,17 @@ class Decode(object):
     Diverse beam search: BEAM with ``groups`` = (G, fp32 λ) — part of the key; ``n_best`` is then the rows returned per group.
     Constrained beam search: BEAM with ``cons``, this call's (T, CONS_MAX, CONS_LEN) int32 host table of ``ops.check_constraints`` (a
     captured input, like ``given``); only the fact that the decode is constrained is part of the key.
-    Stochastic beam search: BEAM with ``stochastic`` = (τ, m) — part of the key — and ``seed`` as sampling's."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons", "stochastic")
+    Stochastic beam search: BEAM with ``stochastic`` = (τ, m) — part of the key — and ``seed`` as sampling's.
+    Contrastive search: BEAM with ``contrastive`` = (k, fp32 α, m) — part of the key: α is baked into a captured graph, so two α never
+    share one."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons", "stochastic", "contrastive")
 
     def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None,
-                 cons=None, stochastic=None):
+                 cons=None, stochastic=None, contrastive=None):
         self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups, self.cons = (
             kind, width, controls, ctl_key, n_best, sampling, seed, given, groups, cons)
         self.stochastic = stochastic
+        self.contrastive = contrastive
 
     @property
     def constrained(self):
@@ -261,12 +290,13 @@ class Decode(object):
     @property
     def ranked(self):
         """decoding controls and / or n-best: lengths tracked, all B final hypotheses sorted by their key"""
-        return self.kind == BEAM and self.stochastic is None and (self.n_best > 0 or self.ctl_key is not None)
+        return self.kind == BEAM and self.stochastic is None and self.contrastive is None and (self.n_best > 0 or self.ctl_key is not None)
 
     @property
     def key(self):
         return ((self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
-                + (("constrained",) if self.constrained else ()) + ((("stochastic",) + tuple(self.stochastic),) if self.stochastic is not None else ()))
+                + (("constrained",) if self.constrained else ()) + ((("stochastic",) + tuple(self.stochastic),) if self.stochastic is not None else ())
+                + ((("contrastive",) + tuple(self.contrastive),) if self.contrastive is not None else ()))
 
 
 class DecodePlan(object):
@@ -282,6 +312,7 @@ class DecodePlan(object):
                  "cons",                                        # constrained beam search: the (T, 4, 4) device table, a captured input
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
                  "stochastic",                                  # stochastic beam search: ops.stochastic_beam_step's keywords (+ the seed words)
+                 "contrastive",                                 # contrastive search: ops.contrastive_step's keywords
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
                  "raw",                                         # forced pass stopped at the score matrix (``teacher_scores``)
                  "seq_cross", "seq_self",                       # segmentations, built on first use
@@ -333,20 +364,25 @@ class _DecoderSide(object):
             proj = ops.take_rows_f32(proj.reshape(self.T, -1), sent).view(rd.n, *proj.shape[1:]) if proj is not None else None
         return ops.split_cols(wide[0], len(self.layers)) if self.stacked else wide, bank, proj
 
-    def scores(self, rows, ptr, nxt, i, caches, seq_self, seq_cross, key_rows=None, group=1):
+    def scores(self, rows, ptr, nxt, i, caches, seq_self, seq_cross, key_rows=None, group=1, hidden=False, head=True):
         """one decoding iteration over hypothesis rows → their score rows: the text embedding of tokens ``nxt`` at position i (a row of the
         per-checkpoint table: one gather instead of LayerNorm(300) → projection → LayerNorm + position encoding), the layers over each
         row's ancestry ``key_rows`` in the KV caches (``group`` rows per sentence share its memory K|V; greedy: no table, group 1), then
         the head — raw logits in ``video`` mode (the step score is their log_softmax; translator.py:159) — or the pointer-generator's
-        probabilities"""
+        probabilities.  ``hidden`` (contrastive search): → (score rows, the last layer's output the head reads); with ``head=False``
+        the head is not run and the score rows are None (the last position commits a word and expands nothing)."""
         model, cx = self.model, self.cx
         mem_kv, bank, proj = rows
         x = ops.take_rows(self.tab[i], nxt) if self.tab is not None else model.text_embeddings.run_at(nxt, i, cx)
         for layer, cache, kv in zip(self.layers, caches, mem_kv):
             x = layer.step(x, i, model.config.max_t_len, cache, kv, seq_self, seq_cross, cx, key_rows=key_rows, q_group=group)
+        if not head:
+            return None, x
         if model.config.model_mode == "video":
-            return model.decoder_classifier.run(x, cx.eps)
-        return model._lm_probs(x, bank, ptr, cx, proj=proj)[0]
+            sc = model.decoder_classifier.run(x, cx.eps)
+        else:
+            sc = model._lm_probs(x, bank, ptr, cx, proj=proj)[0]
+        return (sc, x) if hidden else sc
 
 
 class Translator(object):
@@ -554,6 +590,26 @@ class Translator(object):
         W = s["beam_size"]
         return self._translate(model_inputs, self.model, decode=Decode(BEAM, W, n_best=W, seed=s["seed"],
                                                                        stochastic=(s["random_sampling_temp"], s["min_length"])))
+
+    @torch.no_grad()
+    def translate_batch_contrastive(self, model_inputs, top_k=None, penalty_alpha=None, min_length=None, **unknown):
+        """Contrastive search (module docstring): at every position the model's k = ``top_k`` most probable words are run
+        through the decoder and the one with the highest (1 − α)·p − α·max cos(its hidden state, the caption's earlier ones) is kept, α =
+        ``penalty_alpha`` (defaults ``opt.top_k`` = 4, ``opt.penalty_alpha`` = 0.6, ``opt.min_length`` = 0) → (dec_seq_list,
+        oov_word_dict, score_list, length_list, penalty_list): per video ids (S_b, Lt) int64 (BOS first, PAD after EOS), cum (S_b,) fp32
+        (the model's summed step scores, what ``score_captions`` reproduces), len (S_b,) int64 and pen (S_b, Lt) fp32, the kept words'
+        penalties (0 at position 0 and after the end).  Deterministic; one caption per sentence.  ValueError on the host for k, α,
+        ``min_length`` and rows wider than 4096 columns; TypeError for any other keyword; ``incremental=False`` raises
+        NotImplementedError."""
+        if unknown:
+            raise TypeError("unknown contrastive search keyword(s): %s" % ", ".join(sorted(unknown)))
+        c = ops.check_contrastive(self.max_t_len, top_k if top_k is not None else getattr(self.opt, "top_k", 4),
+                                  penalty_alpha if penalty_alpha is not None else getattr(self.opt, "penalty_alpha", 0.6),
+                                  min_length if min_length is not None else getattr(self.opt, "min_length", 0), self._max_cols(model_inputs))
+        if not self.incremental:
+            raise NotImplementedError("contrastive search decodes incrementally only (Translator(incremental=True))")
+        return self._translate(model_inputs, self.model, decode=Decode(BEAM, c["top_k"], contrastive=(
+            c["top_k"], c["penalty_alpha"], c["min_length"])))
 
     @staticmethod
     def _clean(dec_seq_list, row, remove_dup=True):
@@ -767,6 +823,9 @@ class Translator(object):
             temp, m = decode.stochastic
             dp.stochastic = dict(temp=temp, min_length=m, max_cols=dp.ptr_hyp["c_max"])
             dp.seed_src, dp.seed_used = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+        if decode.contrastive is not None:     # (k is the plan's width; α and m travel by value into every launch)
+            _, alpha, m = decode.contrastive
+            dp.contrastive = dict(alpha=alpha, min_length=m, max_cols=dp.ptr_hyp["c_max"])
         if len(self._preps) > 32:
             self._preps.clear()
         self._preps[key] = dp
@@ -866,6 +925,7 @@ class Translator(object):
         else:
             side = self._side(model, dp, enc, cx)
             loop = (self._sample_iterations if dp.kind == SAMPLE else self._paragraph_iterations if dp.rounds is not None else
+                    self._contrastive_iterations if dp.contrastive is not None else
                     self._beam_iterations if dp.kind == BEAM else self._greedy_iterations)
             out = loop(dp, side)
         stamp()
@@ -1127,6 +1187,44 @@ class Translator(object):
                                      text, ext, dp.seed_used, **dp.sampling)
         return ext.view(T, R, Lt), cum.view(T, R), length.view(T, R)
 
+    @staticmethod
+    def _contrastive_iterations(dp, side):
+        """A contrastive search: Lt decoder passes over the T·k candidate rows — one more than the other loops, because a word is chosen
+        by its own hidden state, so the word at position Lt − 1 needs a pass too (without the head: it expands nothing) — each followed
+        by ``ops.contrastive_step``, which commits the winner of every sentence and hands its top-k continuations to the k rows.  Row 0
+        of a sentence starts alone live on BOS (p 1, step score 0); the ping-pong pairs are the beam decode's; the state is per sentence.
+        There is no final pick → (ids (T, 1, Lt) int32, cum (T, 1) fp32, len (T, 1) int32, pen (T, 1, Lt) fp32)."""
+        cfg = side.model.config
+        k, T, Lt, D, dev = dp.width, dp.T, cfg.max_t_len, cfg.hidden_size, side.wide[0].device
+        R = T * k
+        toks = [[torch.full((R, Lt), PAD, dtype=torch.int32, device=dev) for _ in range(3)] for _ in range(2)]
+        toks[0][0][:, 0] = BOS
+        toks[0][1][:, 0] = BOS
+        toks[0][2][:, 0] = torch.arange(R, dtype=torch.int32, device=dev) * Lt
+        cand_p = torch.zeros(T, k, dtype=torch.float32, device=dev)
+        cand_p[:, 0] = 1.0                                                     # iteration 0: row 0 alone
+        cand_score = torch.full((T, k), float("-inf"), dtype=torch.float32, device=dev)
+        cand_score[:, 0] = 0.0
+        cand_p, cand_score = cand_p.view(R), cand_score.view(R)
+        ids = torch.full((T, Lt), PAD, dtype=torch.int32, device=dev)
+        cum = torch.zeros(T, dtype=torch.float32, device=dev)
+        length = torch.zeros(T, dtype=torch.int32, device=dev)
+        pen = torch.zeros(T, Lt, dtype=torch.float32, device=dev)
+        fin = torch.zeros(T, dtype=torch.int32, device=dev)
+        hist = torch.zeros(T, Lt, D, dtype=torch.float32, device=dev)
+        hist_n2 = torch.zeros(T, Lt, dtype=torch.float64, device=dev)
+        nxt = torch.full((R,), BOS, dtype=torch.int32, device=dev)
+        caches, rows, seq_cross = side.caches(R), side.rows(), side.seq_cross(dp)
+        if dp.seq_self is None:        # this decode's own list: Lt entries, the last one over Lt keys
+            dp.seq_self = [SeqInfo.uniform(R, 1, i + 1, dev) for i in range(Lt)]
+        for i in range(Lt):
+            t_in, t_out = toks[i % 2], toks[(i + 1) % 2]
+            scores, x = side.scores(rows, dp.ptr_hyp, nxt, i, caches, dp.seq_self[i], seq_cross, t_in[2], k, hidden=True, head=i + 1 < Lt)
+            _, _, _, nxt = ops.contrastive_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, k, i, side.logits, UNK, EOS, PAD, ops.to_f32(x),
+                                                cand_p, cand_score, ids, cum, length, pen, fin, hist, hist_n2, t_in, t_out, Lt,
+                                                **dp.contrastive)
+        return ids.unsqueeze(1), cum.unsqueeze(1), length.unsqueeze(1), pen.unsqueeze(1)
+
     def _seed_word_on(self, dev):
         """the sampling decodes' seed word (int64 (1,) on ``dev``): drawn once from torch's default generator, then advanced on the device
         by every decode with seed=None; a captured graph holds its address"""
@@ -1149,6 +1247,8 @@ class Translator(object):
             raise RuntimeError("sampling decodes on the GPU only (no CPU fallback exists)")
         if decode.stochastic is not None and dev.type != "cuda":
             raise ops._lib.SvpcKernelError("stochastic beam search decodes on the GPU only (no CPU fallback exists)")
+        if decode.contrastive is not None and dev.type != "cuda":
+            raise ops._lib.SvpcKernelError("contrastive search decodes on the GPU only (no CPU fallback exists)")
         if decode.kind == FORCE and dev.type != "cuda":
             raise ops._lib.SvpcKernelError("forced scoring runs on the GPU only (no CPU fallback exists)")
         # the text half of every step's ids / masks is blanked in place, as the reference does (translator.py:205-228).  When the per-step
@@ -1217,12 +1317,15 @@ class Translator(object):
         # every strategy's result: ids (T, K, Lt), cum (T, K) or None, len (T, K) or None.  The call returns the first n_best of the K rows
         # per sentence, or (n_best 0) the chosen caption alone, without lengths
         k = decode.n_best
-        res, scores, lens, mets, gums, logqs = [], [], [], [], [], []
+        res, scores, lens, mets, gums, logqs, pens = [], [], [], [], [], [], []
         for plan, out in plans_outs:
             ids, cum, length = out[:3]
             met = out[3][:, :k].to(torch.int64) if decode.constrained else None
             gum, logq = (out[3], out[4]) if decode.stochastic is not None else (None, None)
-            if k and decode.groups is not None and k < decode.width // decode.groups[0]:      # the first k rows of every group
+            pen = out[3][:, 0] if decode.contrastive is not None else None
+            if decode.contrastive is not None:         # one caption per sentence, with its length
+                ids, cum, length = ids[:, 0], cum[:, 0].contiguous(), length[:, 0].to(torch.int64)
+            elif k and decode.groups is not None and k < decode.width // decode.groups[0]:      # the first k rows of every group
                 G, Bg = decode.groups[0], decode.width // decode.groups[0]
                 ids, cum, length = (v.reshape(v.shape[0], G, Bg, *v.shape[2:])[:, :, :k].reshape(v.shape[0], G * k, *v.shape[2:])
                                     for v in (ids, cum, length))
@@ -1236,9 +1339,11 @@ class Translator(object):
             ids = ids.to(torch.int64)                  # (one cast per part: the per-video results are views of it)
             for b in range(plan.N):
                 o, n_ = plan.h_step_off[b], plan.h_step_len[b]
-                for lst, t in ((res, ids), (scores, cum), (lens, length), (mets, met), (gums, gum), (logqs, logq)):
+                for lst, t in ((res, ids), (scores, cum), (lens, length), (mets, met), (gums, gum), (logqs, logq), (pens, pen)):
                     if t is not None:
                         lst.append(t[o:o + n_])
+        if decode.contrastive is not None:
+            return res, oov_word_dict, scores, lens, pens
         if decode.constrained:
             return res, oov_word_dict, scores, lens, mets
         if decode.stochastic is not None:
