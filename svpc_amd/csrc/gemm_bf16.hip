@@ -324,8 +324,8 @@ int svpc_gemm_mx(const void* A, int a_dt, int lda, int a_kc, const void* B, int 
     const int a_vec = (lda % a_el == 0) && ((((uintptr_t)A) & 15) == 0);
     const int b_vec = (ldb % b_el == 0) && ((((uintptr_t)B) & 15) == 0);
     const bool full = (M % BMN == 0) && (N % BMN == 0) && (K % k_chunk == 0) && (k_chunk % GBK == 0) && a_vec && b_vec;
-    static int remap = -1, nwn_env = -1;
-    if (remap < 0) { const char* e = getenv("SVPC_GEMM_REMAP"); remap = e ? atoi(e) : 1; }
+    const int remap = gemm_remap_env();
+    static int nwn_env = -1;
     if (nwn_env < 0) { const char* e = getenv("SVPC_GEMM_NWN"); nwn_env = e ? atoi(e) : 0; }
     // 8 waves (64×32 per wave) hide the staging latency better when A is k-contiguous and the grid is not huge;
     // the transposed-read (wgrad) and very wide problems run better with 4 waves of 64×64

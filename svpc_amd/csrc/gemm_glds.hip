@@ -820,8 +820,7 @@ int svpc_gemm_glds_rg(const void* A, int lda, int a_kc, const void* B, int ldb, 
     }
     int k_chunk = ceil_div(ceil_div(K, splitk), GL_BK) * GL_BK;
     splitk = ceil_div(K, k_chunk);
-    static int remap = -1;
-    if (remap < 0) { const char* e = getenv("SVPC_GEMM_REMAP"); remap = e ? atoi(e) : 1; }
+    const int remap = gemm_remap_env();
     static int ppdbg = -1;
     if (ppdbg < 0) { const char* e = getenv("SVPC_PP_DBG"); ppdbg = e ? atoi(e) : 0; }
     static int p8_env = -1;

@@ -854,10 +854,10 @@ static int gemm_l32_x(const float* A, int lda, int a_kc, const float* B, int ldb
                  "gemm_l32: needs K % 32 == 0 (or both operands k-contiguous and K % 4 == 0) and 16-byte aligned fp32 rows");
     SVPC_REQUIRE(p_drop <= 0.f || seed != nullptr, "gemm: dropout needs a seed pointer");
     Epi epi{bias, act, p_drop, site, seed, accumulate, Z, R, G, gact};
-    static int env_tile = -1, env_split = -1, remap = -1;
+    static int env_tile = -1, env_split = -1;
+    const int remap = gemm_remap_env();
     if (env_tile < 0) { const char* e = getenv("SVPC_L32_TILE"); env_tile = e ? atoi(e) : 0; }      // 128 | 64 (deep ring) | 65 (64, 4 stages)
     if (env_split < 0) { const char* e = getenv("SVPC_L32_SPLITK"); env_split = e ? atoi(e) : 0; }
-    if (remap < 0) { const char* e = getenv("SVPC_GEMM_REMAP"); remap = e ? atoi(e) : 1; }
     static int env_skinny = -1;
     if (env_skinny < 0) { const char* e = getenv("SVPC_L32_SKINNY"); env_skinny = e ? atoi(e) : 1; }
     static int skinny_m = -1;

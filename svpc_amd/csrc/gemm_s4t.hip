@@ -12,27 +12,10 @@
 // chunk c of k-row r kept at slot c ^ 2·((r & 3) | ((r >> 1) & 4))) read through ds_read_b64_tr_b16.
 // Epilogue: fp32 sums through a wave-private LDS image, + R, one rounding to bf16, whole 128-byte lines.
 #include "gemm_common.h"
-#include <stdlib.h>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef short short4s __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1))) * s4t_gptr;
-typedef void __attribute__((address_space(3))) * s4t_lptr;
 
 constexpr int S4T_BK = 64;
 constexpr int S4T_HALF = 128 * S4T_BK * 2;      // 16 KiB: the A tile image, the B tile image
 constexpr int S4T_STAGE = 2 * S4T_HALF;
-
-__device__ __forceinline__ bf16x8 s4t_frag_tr(const char* __restrict__ a) {      // rows r..r+3 (this call) and r+4..r+7 of a lane's column
-    typedef short4s __attribute__((address_space(3))) * lds_ptr;
-    const short4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(a));
-    const short4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)(a + 4 * 256));
-    union { short s[8]; bf16x8 v; } u;
-    u.s[0] = lo[0]; u.s[1] = lo[1]; u.s[2] = lo[2]; u.s[3] = lo[3];
-    u.s[4] = hi[0]; u.s[5] = hi[1]; u.s[6] = hi[2]; u.s[7] = hi[3];
-    return u.v;
-}
 
 template <bool HASR, int NS>
 __global__ __launch_bounds__(512, NS == 2 ? 2 : 1) void gemm_s4t_kernel(const __bf16* __restrict__ A, int lda, const __bf16* __restrict__ B, int ldb,
@@ -55,8 +38,7 @@ __global__ __launch_bounds__(512, NS == 2 ? 2 : 1) void gemm_s4t_kernel(const __
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int kr = 8 * wave + 4 * u + (lane >> 4);
-        const int fx = 2 * ((kr & 3) | ((kr >> 1) & 4));
-        const int col = min(n0 + 8 * ((lane & 15) ^ fx), N - 8);      // columns past N are clamped (their sums are never stored)
+        const int col = min(n0 + 8 * ((lane & 15) ^ tr_swizzle(kr)), N - 8);      // columns past N are clamped (their sums are never stored)
         gb[u] = B + (size_t)kr * ldb + col;
     }
     const size_t stepB = (size_t)S4T_BK * ldb;
@@ -64,21 +46,16 @@ __global__ __launch_bounds__(512, NS == 2 ? 2 : 1) void gemm_s4t_kernel(const __
     do {                                                                                                                          \
         char* st_ = smem + ((t) % NS) * S4T_STAGE;                                                                                \
         const __bf16* sa_ = ga + (size_t)(t) * S4T_BK;                                                                            \
-        __builtin_amdgcn_global_load_lds((s4t_gptr)(sa_), (s4t_lptr)(st_ + ((wave * 2) << 10)), 16, 0, 0);                        \
-        __builtin_amdgcn_global_load_lds((s4t_gptr)(sa_ + 32), (s4t_lptr)(st_ + ((wave * 2 + 1) << 10)), 16, 0, 0);               \
-        __builtin_amdgcn_global_load_lds((s4t_gptr)(gb[0] + (size_t)(t) * stepB), (s4t_lptr)(st_ + S4T_HALF + wave * 2048), 16, 0, 0);        \
-        __builtin_amdgcn_global_load_lds((s4t_gptr)(gb[1] + (size_t)(t) * stepB), (s4t_lptr)(st_ + S4T_HALF + wave * 2048 + 1024), 16, 0, 0); \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(sa_), (gemm_lptr)(st_ + ((wave * 2) << 10)), 16, 0, 0);                        \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(sa_ + 32), (gemm_lptr)(st_ + ((wave * 2 + 1) << 10)), 16, 0, 0);               \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(gb[0] + (size_t)(t) * stepB), (gemm_lptr)(st_ + S4T_HALF + wave * 2048), 16, 0, 0);        \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(gb[1] + (size_t)(t) * stepB), (gemm_lptr)(st_ + S4T_HALF + wave * 2048 + 1024), 16, 0, 0); \
     } while (0)
     // ---- fragment reads.  A: block `blk` (16 rows), k block kb; lane: row lane&15, logical chunk lane>>4
-    const int fr_off = (lane & 15) * 64 + ((((lane >> 4) ^ (((lane >> 3) & 1) << 1))) << 4);
-#define S4T_FRAGA(img, blk, kb) (*reinterpret_cast<const bf16x8*>((img) + (((blk) * 2 + (kb)) << 10) + fr_off))
-    // B: 16-column block cb (0..7) and k block kb of the [64][128] image; lane (g = lane>>4, q = (lane&15)>>2, p = lane&3) reads k-rows
-    // 32·kb + 8g + q (+4) at logical chunk 2·cb + (p>>1), byte (p&1)·8; both rows share f = 2·(q + 4·(g&1))   (gemm_p8t.hip)
-    const int tg = lane >> 4, tq = (lane & 15) >> 2, tp = lane & 3;
-    const int tfx = 2 * (tq + 4 * (tg & 1));
-    const int tb_off = (8 * tg + tq) * 256 + ((tp & 1) << 3);
-    const int tp1 = tp >> 1;
-#define S4T_FRAGB(img, cb, kb) s4t_frag_tr((img) + (kb) * (32 * 256) + tb_off + (((((2 * (cb)) ^ tfx)) | tp1) << 4))
+    const int fr_off = frag_off(lane);
+    const FragTr tr(lane);
+#define S4T_FRAGA(img, blk, kb) frag_rd(img, blk, kb, fr_off)
+#define S4T_FRAGB(img, cb, kb) tr(img, cb, kb)
 
     floatx4 acc[2][4];
 #pragma unroll
@@ -173,8 +150,8 @@ int svpc_gemm_s4t(const void* A, int lda, const void* B, int ldb, void* C, int l
     SVPC_REQUIRE(svpc_gemm_s4t_supported(lda, ldb, ldc, M, N, K) == 1 &&
                      ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)R)) & 15) == 0,
                  "gemm_s4t: needs K % 64 == 0, N % 8 == 0, 16-byte aligned bf16 rows");
-    static int remap = -1, deep_max = -1;
-    if (remap < 0) { const char* e = getenv("SVPC_GEMM_REMAP"); remap = e ? atoi(e) : 1; }
+    const int remap = gemm_remap_env();
+    static int deep_max = -1;
     if (deep_max < 0) { const char* e = getenv("SVPC_S4T_DEEP_MAX"); deep_max = e ? atoi(e) : 256; }
     const int tiles_m = ceil_div(M, 128), tiles_n = ceil_div(N, 128);
     const bool deep = tiles_m * tiles_n <= deep_max;     // at most one workgroup per CU anyway: four stages

@@ -13,40 +13,11 @@
 // leaves at most one workgroup per CU anyway (three slices in flight).  Epilogue as gemm_p8x3.hip (bias, ReLU / GELU, hi / lo planes
 // through a wave-private LDS image, whole-line stores; optional plain-bf16 pre-activation copy Z).
 #include "gemm_common.h"
-#include <stdlib.h>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1))) * s4_gptr;
-typedef void __attribute__((address_space(3))) * s4_lptr;
 
 constexpr int S4_BK = 64;            // width of a staged tile image: 2 planes × 32 k
 constexpr int S4_KS = 32;            // k-slice per staged buffer
 constexpr int S4_HALF = 128 * S4_BK * 2;      // 16 KiB: 128 rows × 64 k
 constexpr int S4_STAGE = 2 * S4_HALF;         // A tile + B tile
-
-__device__ __forceinline__ uint32_t s4_pack2(float lo, float hi) {
-    union { __bf16 h[2]; uint32_t u; } pk;
-    pk.h[0] = (__bf16)lo; pk.h[1] = (__bf16)hi;
-    return pk.u;
-}
-__device__ __forceinline__ float s4_lo(float v) { return v - (float)(__bf16)v; }
-__device__ __forceinline__ float s4_gelu(float x) {      // erf by Abramowitz-Stegun 7.1.26 (|error| ≤ 1.5e-7), as gemm_p8x3.hip
-    const float u = x * 0.70710678118654752f, au = fabsf(u);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, au, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    const float e = __expf(-au * au);
-    return 0.5f * x * (1.0f + copysignf(fmaf(-p * t, e, 1.0f), u));
-}
-template <int ACT>
-__device__ __forceinline__ float s4_act(float z) {
-    if (ACT == ACT_RELU) return fmaxf(z, 0.f);
-    if (ACT == ACT_GELU) return s4_gelu(z);
-    return z;
-}
 
 // one epilogue pass over the wave's 32×64 block: MODE 0 bf16(z) | 1 hi plane of act(z) | 2 lo plane → wave-private LDS image
 // [32 rows][128 B] (16-byte chunk c of row r kept at c ^ (r & 7)) → whole 128-byte lines
@@ -60,10 +31,10 @@ __device__ __forceinline__ void s4_store_pass(const floatx4 (&acc)[2][4], __bf16
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float z0 = acc[i][j][0] + bb[j].x, z1 = acc[i][j][1] + bb[j].y, z2 = acc[i][j][2] + bb[j].z, z3 = acc[i][j][3] + bb[j].w;
-            if (MODE != 0) { z0 = s4_act<ACT>(z0); z1 = s4_act<ACT>(z1); z2 = s4_act<ACT>(z2); z3 = s4_act<ACT>(z3); }
-            if (MODE == 2) { z0 = s4_lo(z0); z1 = s4_lo(z1); z2 = s4_lo(z2); z3 = s4_lo(z3); }
+            if (MODE != 0) { z0 = gemm_act<ACT>(z0); z1 = gemm_act<ACT>(z1); z2 = gemm_act<ACT>(z2); z3 = gemm_act<ACT>(z3); }
+            if (MODE == 2) { z0 = bf16_lo(z0); z1 = bf16_lo(z1); z2 = bf16_lo(z2); z3 = bf16_lo(z3); }
             uint2 v;
-            v.x = s4_pack2(z0, z1); v.y = s4_pack2(z2, z3);
+            v.x = pack2(z0, z1); v.y = pack2(z2, z3);
             const int c16 = j * 2 + (q >> 1);
             *reinterpret_cast<uint2*>(wl + r * 128 + ((c16 ^ (r & 7)) << 4) + ((q & 1) << 3)) = v;
         }
@@ -105,10 +76,10 @@ __global__ __launch_bounds__(512, NS == 2 ? 2 : 1) void gemm_s4x3_kernel(const _
     do {                                                                                                                          \
         char* da_ = smem + ((t) % NS) * S4_STAGE + ((wave * 2) << 10);                                                            \
         const size_t o_ = (size_t)(t) * S4_KS;                                                                                    \
-        __builtin_amdgcn_global_load_lds((s4_gptr)(ga + o_), (s4_lptr)(da_), 16, 0, 0);                                           \
-        __builtin_amdgcn_global_load_lds((s4_gptr)(ga + o_ + a_lo), (s4_lptr)(da_ + 1024), 16, 0, 0);                             \
-        __builtin_amdgcn_global_load_lds((s4_gptr)(gb + o_), (s4_lptr)(da_ + S4_HALF), 16, 0, 0);                                 \
-        __builtin_amdgcn_global_load_lds((s4_gptr)(gb + o_ + b_lo), (s4_lptr)(da_ + S4_HALF + 1024), 16, 0, 0);                   \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(ga + o_), (gemm_lptr)(da_), 16, 0, 0);                                           \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(ga + o_ + a_lo), (gemm_lptr)(da_ + 1024), 16, 0, 0);                             \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(gb + o_), (gemm_lptr)(da_ + S4_HALF), 16, 0, 0);                                 \
+        __builtin_amdgcn_global_load_lds((gemm_gptr)(gb + o_ + b_lo), (gemm_lptr)(da_ + S4_HALF + 1024), 16, 0, 0);                   \
     } while (0)
     // fragment: block `blk` (16 rows) and k block kb of an image; lane: row lane&15, logical chunk lane>>4
     const int fr_off = (lane & 15) * 64 + ((((lane >> 4) ^ (((lane >> 3) & 1) << 1))) << 4);
@@ -179,8 +150,7 @@ int svpc_gemm_s4x3(const void* A, int lda, int a_lo, const void* B, int ldb, lon
                      ((((uintptr_t)A) | ((uintptr_t)B) | ((uintptr_t)C) | ((uintptr_t)Z) | ((uintptr_t)bias)) & 15) == 0 &&
                      (act == ACT_RELU || act == ACT_GELU || (act == ACT_NONE && Z == nullptr)) && (Z == nullptr || ldz >= N),
                  "gemm_s4x3: needs K % 32 == 0, K >= 64, N % 8 == 0, 16-byte aligned split rows (lo plane behind the hi plane), act in {none, relu, gelu}");
-    static int remap = -1;
-    if (remap < 0) { const char* e = getenv("SVPC_GEMM_REMAP"); remap = e ? atoi(e) : 1; }
+    const int remap = gemm_remap_env();
     const int tiles_m = ceil_div(M, 128), tiles_n = ceil_div(N, 128);
     // at most one workgroup per CU anyway (the decoder's N = 768 projections: 198): four stages, three k-tiles in flight
     static int deep_max = -1;
