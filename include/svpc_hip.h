@@ -804,6 +804,24 @@ int svpc_seq_kd_bwd(const float* scores, int ld, const float* tq, int ldq, const
                     const int* barred, const float* row_w, const float* row_v, const float* dl, int n_cap, int lt, int logits,
                     int teacher_logits, int unk, float* dscores, int ld_out, svpc_stream_t stream);
 
+/* ---- contrastive (SimCTG) training loss on the decoder's last-layer hidden states (Su et al. 2022), the training
+ *      counterpart of svpc_contrastive_step.  hidden row r·lt + i (d floats, row stride ld_h) is h_i of caption row r; the caption's token
+ *      set is positions 0 … len[r] (svpc_force_inputs' length, clamped into [0, lt − 1] on the device), n = len[r] + 1; 2 <= lt <= 32,
+ *      1 <= d <= ld_h, lt·d·4 bytes <= 144 KB (the rows live in LDS), margin finite in (0, 2].  In fp64: q_i = |h_i|² and the dot
+ *      products in svpc_contrastive_step's order (a q_i has hist_n2's bits); c_ij = h_i·h_j / (sqrt(q_i)·sqrt(q_j)), 0 when a norm is 0;
+ *      m_ij = (margin − 1) + c_ij; the ordered pair (i, j), i != j, is active iff m_ij > 0. */
+/* cl (n_cap,) = fp32(sum over i != j of max(0, m_ij) / (n(n − 1))), sim (n_cap,) = fp32(the mean of c_ij over i != j), nact (n_cap,) = the
+ * active ordered pairs — all 0 for n < 2 —, q (n_cap, lt) fp64 = q_i (0 past the end), loss (1,) = fp32(sum of row_v·cl), products and
+ * sums in fp64 in svpc_seq_nll_fwd's order.  No atomics: the same inputs give the same bits.  n_cap = 0: loss = 0.  Two launches. */
+int svpc_seq_cl_fwd(const float* hidden, int ld_h, int d, const int* len, const float* row_v, int n_cap, int lt, double margin, float* cl,
+                    float* sim, int* nact, double* q, float* loss, svpc_stream_t stream);
+/* dh (n_cap·lt rows of ld_out >= d floats) = d loss / d hidden times the device scalar dl (1,), every element written:
+ * dl·row_v[r]·(2 / (n(n − 1)))·(g_i − (g_i·u_i)·u_i) / sqrt(q_i) with u_i = h_i / sqrt(q_i) and g_i = the sum of u_j over the active pairs
+ * (i, j), in fp64 and rounded once; 0 from column d up, for a zero row, past the caption's end and for n < 2.  The Gram matrix is
+ * recomputed from the hidden rows (nothing else is saved).  n_cap = 0 returns 0.  One launch. */
+int svpc_seq_cl_bwd(const float* hidden, int ld_h, int d, const int* len, const float* row_v, const float* dl, int n_cap, int lt,
+                    double margin, float* dh, int ld_out, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

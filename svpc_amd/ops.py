@@ -3670,3 +3670,101 @@ def seq_kd(scores, row_c, tgt, length, tq, row_w, row_v, logits, teacher_logits,
     _need_gpu(scores)
     return _SeqKd.apply(_c(scores), rc.dev(scores.device), tgt, length, tq.detach(), row_w, row_v, 1 if logits else 0,
                         1 if teacher_logits else 0, int(unk_id), max_c)
+
+
+# ------------------------------------------------------------------------------------------------ contrastive (SimCTG) training
+CL_MAX_LT = 32                  # a row's active partners are one 32-bit mask (svpc_seq_cl_fwd)
+CL_ROW_BYTES = 144 * 1024       # a caption's Lt rows of D floats live in LDS
+
+
+def check_simctg(margin=None, cl_weight=None, weights=None, cl_weights=None, shape=None, row_v=None, rows=None, device=None, need_gpu=True):
+    """Host checks of contrastive (SimCTG) training (ValueError for each): ``margin`` a finite number in (0, 2] → its
+    fp32-rounded value (a float); ``cl_weight`` finite and not negative; ``weights`` / ``cl_weights`` floating point of ``shape`` (T, K)
+    or (T·K,); ``row_v`` contiguous fp32 (``rows``,) on ``device``.  ``SvpcKernelError`` for a tensor that is not on the GPU (no CPU
+    fallback exists), unless ``need_gpu`` is off (a caller whose other checks come first)."""
+    rho = None
+    if margin is not None:
+        if isinstance(margin, bool) or not isinstance(margin, numbers.Real) or not math.isfinite(margin) or not 0.0 < margin <= 2.0:
+            raise ValueError("margin must be a finite number in (0, 2], got %r" % (margin,))
+        rho = float(torch.tensor(float(margin), dtype=torch.float32))
+        if not rho > 0.0:
+            raise ValueError("margin must be a finite number in (0, 2] after rounding to fp32, got %r" % (margin,))
+    if cl_weight is not None and (isinstance(cl_weight, bool) or not isinstance(cl_weight, numbers.Real) or not math.isfinite(cl_weight)
+                                  or cl_weight < 0):
+        raise ValueError("cl_weight must be a finite number >= 0, got %r" % (cl_weight,))
+    for name, t in (("weights", weights), ("cl_weights", cl_weights)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_floating_point()
+                              or (shape is not None and tuple(t.shape) not in (tuple(shape), (shape[0] * shape[1],)))):
+            raise ValueError("%s must be a floating point tensor%s, got %s"
+                             % (name, " of shape %s or (%d,)" % (tuple(shape), shape[0] * shape[1]) if shape is not None else "",
+                                "%s %s" % (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__))
+    if row_v is not None and (not torch.is_tensor(row_v) or not _row_vec(row_v, rows, torch.float32, device)):
+        raise ValueError("row_v must be contiguous fp32 (%s,) on the hidden rows' device" % (rows,))
+    for t in (weights, cl_weights, row_v):
+        if need_gpu and t is not None and not t.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.ops: contrastive training runs on the GPU only (no CPU fallback exists)")
+    return rho
+
+
+class _SeqCl(Function):
+    @staticmethod
+    def forward(ctx, hidden, length, row_v, rho, lt):
+        R = length.shape[0]
+        dev = hidden.device
+        cl = torch.empty(R, dtype=torch.float32, device=dev)
+        sim = torch.empty(R, dtype=torch.float32, device=dev)
+        nact = torch.empty(R, dtype=torch.int32, device=dev)
+        q = torch.empty(R, lt, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_cl_fwd", _p(hidden), hidden.stride(0), hidden.shape[1], _p(length), _p(row_v), R, lt, rho, _p(cl), _p(sim), _p(nact),
+                  _p(q), _p(loss), _stream())
+        ctx.save_for_backward(hidden, length, row_v)
+        ctx.cfg = (R, lt, rho)
+        ctx.mark_non_differentiable(cl, sim, nact, q)
+        ctx.set_materialize_grads(False)
+        return loss, cl, sim, nact, q
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 5
+        hidden, length, row_v = ctx.saved_tensors
+        R, lt, rho = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dh = torch.empty(hidden.shape, dtype=torch.float32, device=hidden.device)          # (every element is written by the kernel)
+        if hidden.shape[0] > R * lt:
+            dh[R * lt:].zero_()
+        _lib.call("seq_cl_bwd", _p(hidden), hidden.stride(0), hidden.shape[1], _p(length), _p(row_v), _p(dl), R, lt, rho, _p(dh), dh.shape[1],
+                  _stream())
+        return dh, None, None, None, None
+
+
+def seq_cl(hidden, length, row_v, margin, lt, with_norms=False):
+    """The contrastive (SimCTG) loss of given captions on the decoder's last-layer hidden states (svpc_seq_cl_fwd / _bwd),
+    differentiable in ``hidden`` only: ``hidden`` (≥ R·Lt, D) fp32, unit column stride, any row stride ≥ D — row r·Lt + i is position i of
+    caption row r —, ``length`` (R,) int32 as ``force_inputs`` returns it (the caption's token set is positions 0 … length, clamped into
+    [0, Lt − 1] on the device), ``row_v`` (R,) fp32 weights, ``margin`` ρ in (0, 2] (rounded to fp32), 2 ≤ ``lt`` ≤ 32 → (loss () fp32 =
+    Σ v_r·cl_r, cl (R,) fp32 the mean over the caption's ordered token pairs of max(0, ρ − 1 + cos(h_i, h_j)), sim (R,) fp32 the mean
+    cosine of those pairs, nact (R,) int32 the pairs with ρ − 1 + cos > 0; all three 0 for a caption of one token).  ``with_norms``: also
+    q (R, Lt) float64, the squared norms |h_i|² in contrastive search's summation order (0 past the end)."""
+    rho = check_simctg(margin=margin)
+    if rho is None:
+        raise ValueError("margin must be a finite number in (0, 2], got None")
+    if isinstance(lt, bool) or not isinstance(lt, numbers.Integral) or not 2 <= int(lt) <= CL_MAX_LT:
+        raise ValueError("seq_cl takes captions of 2..%d positions, got Lt = %r" % (CL_MAX_LT, lt))
+    lt = int(lt)
+    if not torch.is_tensor(hidden) or hidden.dim() != 2 or hidden.dtype != torch.float32 or hidden.shape[1] < 1:
+        raise ValueError("seq_cl: hidden must be fp32 (>= R·Lt, D >= 1) rows (convert a bf16 / split stream with ops.to_f32)")
+    if not torch.is_tensor(length) or length.dim() != 1 or not _row_vec(length, length.shape[0], torch.int32, hidden.device):
+        raise ValueError("seq_cl: length must be contiguous int32 (R,) on the hidden rows' device")
+    R, D = length.shape[0], hidden.shape[1]
+    if hidden.shape[0] < R * lt:
+        raise ValueError("seq_cl: %d caption rows of %d positions need %d hidden rows, got %d" % (R, lt, R * lt, hidden.shape[0]))
+    if lt * D * 4 > CL_ROW_BYTES:
+        raise ValueError("seq_cl: a caption's Lt·D = %d·%d floats do not fit the kernel's %d KB of LDS" % (lt, D, CL_ROW_BYTES // 1024))
+    check_simctg(row_v=row_v, rows=R, device=hidden.device)
+    _need_gpu(hidden)
+    if hidden.stride(1) != 1 or (hidden.shape[0] > 1 and hidden.stride(0) < D):
+        hidden = hidden.contiguous()
+    out = _SeqCl.apply(hidden, length, row_v, rho, lt)
+    return out if with_norms else out[:4]

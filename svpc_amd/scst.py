@@ -55,7 +55,8 @@ def graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="sequ
     """The graded forced pass up to the decoder's score matrix, then ``head``: the encoder side of the decode and the decoder once over all
     positions of the T·K given captions, with gradients.  ``head`` is called inside the pass's ``enable_grad`` with a namespace — ``scores``
     (T·K·Lt, ≥ C) fp32 (probabilities, or raw logits when ``logits``), ``cap_c`` the rows' column counts (an Idx), ``max_cols``, ``tgt``
-    (R, Lt) / ``length`` / ``finished`` (R,) int32 (``ops.force_inputs``'), ``steps`` the videos' sentence counts, ``plan`` the batch structure's plan, ``T``, ``K``, ``Lt`` — and
+    (R, Lt) / ``length`` / ``finished`` (R,) int32 (``ops.force_inputs``'), ``steps`` the videos' sentence counts, ``plan`` the batch structure's plan, ``T``, ``K``, ``Lt``, ``hidden`` (T·K·Lt, D) the decoder's last-layer
+    output the scores are read from (the activation stream's storage: ``ops.to_f32`` makes it fp32) — and
     its result is returned.  ``weights``: what ``ops.check_scst`` is to check beside the captions (``sequence_loss``'s weights)."""
     (input_ids_list, video_features_list, input_masks_list, _tt, ingr_input_ids, _im, ingr_sep_masks, ingr_id_dict, oov_word_dict,
      _al, _ac, batch_step_num) = model_inputs
@@ -124,7 +125,7 @@ def graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="sequ
                 bank = _replicate(bank, K).contiguous()
             scores = model._lm_probs(dec, bank, fp.ptr, cx, proj=proj)[0]
         return head(SimpleNamespace(scores=scores, cap_c=fp.cap_c, max_cols=max(c_list), logits=mode == "video", tgt=tgt, length=length,
-                                    finished=_fin, steps=steps, plan=plan, T=T, K=K, Lt=Lt))
+                                    finished=_fin, steps=steps, plan=plan, T=T, K=K, Lt=Lt, hidden=dec))
 
 
 def sequence_loss(translator, model_inputs, dec_seq_list, weights):
