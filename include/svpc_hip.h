@@ -822,6 +822,23 @@ int svpc_seq_cl_fwd(const float* hidden, int ld_h, int d, const int* len, const 
 int svpc_seq_cl_bwd(const float* hidden, int ld_h, int d, const int* len, const float* row_v, const float* dl, int n_cap, int lt,
                     double margin, float* dh, int ld_out, svpc_stream_t stream);
 
+/* ---- minimum-risk and ranking training over a video's k candidate paragraphs.  Layout, tgt / len / row_w as the sequence
+ *      log-likelihood above with n_cap = n_sent·k caption rows, row t·k + c; the sentences of video b are t = vid_off[b] … vid_off[b + 1] − 1
+ *      (vid_off (n_vid + 1,) rises from 0 to n_sent); cost (n_vid, k) fp64.  In fp64, per video and candidate: s = the sum of cum over the
+ *      video's sentences in order, n = max(1, the sum of len), z = s / n^length_beta (0 when a sentence of the candidate is barred); valid =
+ *      no sentence barred and a finite cost; over the valid candidates, c ascending: q = exp(alpha·(z − max z)) / sum, risk = sum q·cost;
+ *      pos = the valid candidates before this one by (cost, c); the pair (i, j), cost_i < cost_j, is active iff h = z_j − z_i + (pos_j −
+ *      pos_i)·margin > 0, rank = the sum of h over the active pairs (j ascending inside i ascending); G = risk_weight·alpha·q_c·sum_c' q_c'·
+ *      (cost_c − cost_c') + rank_weight·(active pairs with c as j − active pairs with c as i); an invalid candidate has q = 0, no pair, G = 0. */
+/* step / cum / barred as svpc_seq_nll_fwd (the same bits); risk / rank (n_vid,), q / z (n_vid, k) fp64, valid (n_vid, k) int32, w_eff
+ * (n_cap,) = fp32(row_w − G / (n_vid·n^length_beta)) — every element written —; loss (1,) = fp32(−sum row_w·cum over the captions not barred
+ * + (risk_weight·sum risk + rank_weight·sum rank) / n_vid), each sum in svpc_seq_nll_fwd's order (both weights 0: its bits).  The gradient is
+ * svpc_seq_nll_bwd under w_eff.  1 <= k <= 16; alpha, length_beta, margin and the weights finite and >= 0.  Four launches. */
+int svpc_seq_risk_fwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const float* row_w,
+                      const double* cost, const int* vid_off, int n_vid, int n_sent, int k, int lt, int logits, int unk, double alpha,
+                      double length_beta, double margin, double risk_weight, double rank_weight, float* step, float* cum, int* barred,
+                      double* risk, double* rank, double* q, double* z, int* valid, float* w_eff, float* loss, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

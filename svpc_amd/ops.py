@@ -3768,3 +3768,133 @@ def seq_cl(hidden, length, row_v, margin, lt, with_norms=False):
         hidden = hidden.contiguous()
     out = _SeqCl.apply(hidden, length, row_v, rho, lt)
     return out if with_norms else out[:4]
+
+
+# ------------------------------------------------------------------------------------------------ minimum-risk and ranking training
+RISK_MAX = SCST_MAX             # candidates per sentence: one lane each (svpc_seq_risk_fwd)
+RISK_SOURCES = ("sample", "nbest", "diverse", "stochastic")
+
+
+def _risk_number(name, v):
+    if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0):
+        raise ValueError("%s must be a finite number >= 0, got %r" % (name, v))
+
+
+def check_risk(k=None, cost=None, vid_off=None, n_sent=None, alpha=None, length_beta=None, margin=None, risk_weight=None, rank_weight=None,
+               source=None, utility=None, device=None):
+    """Host checks of minimum-risk / ranking training (ValueError for each): ``k`` K in 1 … 16; ``cost`` float64 (N, K)
+    (on ``device``, when given); ``vid_off`` N + 1 host ints (or an Idx) that start at 0, never fall and end at ``n_sent``; ``alpha``,
+    ``length_beta``, ``margin``, ``risk_weight`` and ``rank_weight`` finite and not negative; ``source`` one of the four candidate-set
+    decoders; ``utility`` one of the six score columns.  ``SvpcKernelError`` for a cost that is not on the GPU (no CPU fallback exists).
+    → (K, N, the utility's column or None)."""
+    for name, v in (("alpha", alpha), ("length_beta", length_beta), ("margin", margin), ("risk_weight", risk_weight),
+                    ("rank_weight", rank_weight)):
+        _risk_number(name, v)
+    if source is not None and source not in RISK_SOURCES:
+        raise ValueError("source must be one of %s, got %r" % (", ".join(RISK_SOURCES), source))
+    if utility is not None and utility not in CONSENSUS_UTILITIES:
+        raise ValueError("utility must be one of %s, got %r" % (", ".join(CONSENSUS_UTILITIES), utility))
+    K = N = None
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= RISK_MAX:
+            raise ValueError("risk training takes 1..%d candidates per sentence, got K = %r" % (RISK_MAX, k))
+        K = int(k)
+    if cost is not None:
+        if not torch.is_tensor(cost) or cost.dim() != 2 or cost.dtype != torch.float64:
+            raise ValueError("cost must be float64 (N, K), got %s"
+                             % ("%s %s" % (tuple(cost.shape), cost.dtype) if torch.is_tensor(cost) else type(cost).__name__))
+        N = cost.shape[0]
+        if not 1 <= cost.shape[1] <= RISK_MAX or (K is not None and cost.shape[1] != K):
+            raise ValueError("cost must have one column per candidate (K = %s in 1..%d), got %d" % (K, RISK_MAX, cost.shape[1]))
+        K = cost.shape[1]
+        if device is not None and cost.device != device:
+            raise ValueError("cost must be on the scores' device %s, got %s" % (device, cost.device))
+    if vid_off is not None:
+        off = [int(o) for o in as_idx(vid_off).host]
+        if (not off or off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or (n_sent is not None and off[-1] != n_sent)
+                or (N is not None and len(off) != N + 1)):
+            raise ValueError("vid_off must hold N + 1 = %s offsets that start at 0, never fall and end at the %s sentences, got %r"
+                             % (None if N is None else N + 1, n_sent, off if len(off) <= 20 else off[:20] + ["…"]))
+        N = len(off) - 1
+    if cost is not None and not cost.is_cuda:
+        raise _lib.SvpcKernelError("svpc_amd.ops: risk training runs on the GPU only (no CPU fallback exists)")
+    return K, N, None if utility is None else CONSENSUS_UTILITIES.index(utility)
+
+
+class _SeqRisk(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, cost, off, row_w, logits, unk_id, max_c, params):
+        R, lt = tgt.shape
+        N, K = cost.shape
+        dev = scores.device
+        step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        cum = torch.empty(R, dtype=torch.float32, device=dev)
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        risk = torch.empty(N, dtype=torch.float64, device=dev)
+        rank = torch.empty(N, dtype=torch.float64, device=dev)
+        q = torch.empty(N, K, dtype=torch.float64, device=dev)
+        z = torch.empty(N, K, dtype=torch.float64, device=dev)
+        valid = torch.empty(N, K, dtype=torch.int32, device=dev)
+        w_eff = torch.empty(R, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_risk_fwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(row_w), _p(cost), _p(off), N, R // K, K,
+                  lt, logits, unk_id, *params, _p(step), _p(cum), _p(barred), _p(risk), _p(rank), _p(q), _p(z), _p(valid), _p(w_eff), _p(loss),
+                  _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, w_eff)
+        ctx.cfg = (R, lt, logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred, risk, rank, q, z, valid, w_eff)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred, risk, rank, q, z, valid, w_eff
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 11
+        scores, rc, tgt, length, barred, w_eff = ctx.saved_tensors
+        R, lt, logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        # the objective's derivative in cum is −w_eff: the gradient is seq_nll's under the effective weights, bit for bit
+        _lib.call("seq_nll_bwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(w_eff), _p(dl), R, lt,
+                  logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return (dscores,) + (None,) * 10
+
+
+def seq_risk(scores, row_c, tgt, length, cost, vid_off, row_w, logits, unk_id, alpha, length_beta, margin, risk_weight, rank_weight,
+             max_cols=None):
+    """``seq_nll`` plus the minimum-risk and ranking terms over every video's K candidate paragraphs (svpc_seq_risk_fwd, and svpc_seq_nll_bwd
+    under the effective weights), differentiable in ``scores`` only: caption row r = t·K + k, ``cost`` (N, K) float64 the
+    candidates' costs (a non-finite cost takes its candidate out), ``vid_off`` N + 1 host ints (or an Idx): the sentences of video b are
+    t = vid_off[b] … vid_off[b + 1] − 1, ``row_w`` (R,) fp32 the captions' likelihood weights (None: zeros), the rest as ``seq_nll`` takes
+    it → (loss () fp32 = −Σ w_r·cum_r + (risk_weight·Σ_b risk + rank_weight·Σ_b rank) / N, cum, step, barred as ``seq_nll`` returns them —
+    the same bits —, risk (N,) / rank (N,) / Q (N, K) / z (N, K) float64, valid (N, K) int32, w_eff (R,) fp32: the weights under which
+    ``seq_nll``'s gradient is this loss's).  With both weights zero the loss and its gradient have ``seq_nll``'s bits."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_risk: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_risk: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_risk: length must be contiguous int32 (R,) on the scores' device")
+    K, N, _ = check_risk(cost=cost, alpha=alpha, length_beta=length_beta, margin=margin, risk_weight=risk_weight, rank_weight=rank_weight,
+                         device=scores.device)
+    if R % K:
+        raise ValueError("seq_risk: %d caption rows are no multiple of the K = %d candidates per sentence" % (R, K))
+    off = as_idx(vid_off)
+    check_risk(cost=cost, vid_off=off, n_sent=R // K)
+    if row_w is None:
+        row_w = torch.zeros(R, dtype=torch.float32, device=scores.device)
+    elif not torch.is_tensor(row_w) or not _row_vec(row_w, R, torch.float32, scores.device):
+        raise ValueError("seq_risk: row_w must be contiguous fp32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_risk: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_risk: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    _need_gpu(scores)
+    params = tuple(float(v) for v in (alpha, length_beta, margin, risk_weight, rank_weight))
+    return _SeqRisk.apply(_c(scores), rc.dev(scores.device) if R else None, tgt, length, _c(cost), off.dev(scores.device), row_w,
+                          1 if logits else 0, int(unk_id), max_c, params)
