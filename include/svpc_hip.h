@@ -625,6 +625,28 @@ int svpc_sample_seed(const long long* src, long long* word, long long* used, svp
  * PROBABILITY matrix in both modes: the step kernels take it with logits = 0.  n_rows == 0 returns 0. */
 int svpc_ensemble_combine(const float* const* scores, const int* ld, const double* weights, int n_members, const int* row_c, int rows_per,
                           int n_rows, int max_c, int logits, int unk, int rule, float* out, int ld_out, svpc_stream_t stream);
+/* ---- contrastive decoding (Li et al. 2023; O'Brien & Lewis 2023; with the amateur the same model without the video: visual contrastive
+ * decoding, Leng et al. 2024): an expert's score matrix held against an amateur's, for the same n_rows hypothesis rows.  expert / amateur:
+ * fp32 matrices with leading dimensions ld_e / ld_a, probabilities (logits == 0) or raw logits (logits != 0).  Row r has
+ * C = row_c[r / rows_per] <= max_c columns (max_c 1..4096, within ld_e, ld_a and ld_out).  Coefficients fp64: we > 0, wa >= 0, alpha in
+ * [0, 1], log_alpha = log(alpha) computed on the host (−inf for alpha = 0).  unk is never a candidate: it is left out of every maximum,
+ * head and sum in BOTH score modes, and out[unk] = 0.  The rule, one row at a time:
+ *   1. member log-probabilities, fp64, for c < C, c != unk: probability mode p = raw > 0 ? (double)raw : 0 and l = log p (−inf at 0);
+ *      logits mode l = (double)raw − lse, lse as svpc_ensemble_combine defines it; a member row without a finite non-unk logit is dead:
+ *      l = −inf everywhere;
+ *   2. dead expert row (no column with l_e > −inf): the whole output row is 0;
+ *   3. head H: probability mode p_e,c > 0 and p_e,c >= alpha·p_e,top (one rounded fp64 product); logits mode raw_e,c finite and
+ *      (double)raw_e,c − (double)raw_e,top >= log_alpha; no row reduction other than an exact maximum: bit-reproducible;
+ *   4. amateur term la_c = max(l_a,c, L0), L0 = log(1e-30) = -69.07755278982137 (a zero amateur probability and a dead amateur row
+ *      without an infinity); with wa == 0 the amateur matrix is never read (amateur may be null);
+ *   5. score s_c = we·l_e,c − wa·la_c, the two products and the difference each rounded, never contracted;
+ *   6. normalise: m = max_H s, Z = sum_H exp(s_c − m), out_c = fp32(exp((s_c − m) − log Z)) for c in H; a head of one column gives
+ *      exactly 1.0;
+ *   7. columns outside H, unk, and C <= c < ld_out are 0.
+ * out is a distribution over the head: the step kernels take it with logits = 0.  n_rows == 0 returns 0. */
+int svpc_contrast_combine(const float* expert, int ld_e, const float* amateur, int ld_a, double we, double wa, double alpha,
+                          double log_alpha, const int* row_c, int rows_per, int n_rows, int max_c, int logits, int unk, float* out,
+                          int ld_out, svpc_stream_t stream);
 /* ---- evaluation tail of a decode: the caption the reference submits and its repetition / diversity counts, on the device
  *      (recursive_caption_dataset.py:472-500 convert_ids_to_sentence, src/translate.py:27-42 remove_dup, densevid_eval/evaluateRepetition.py,
  *      evaluateCaptionsDiversity.py:219-282, get_caption_stat.py; the reference copies every sentence to the host, translate.py:81-82).

@@ -16,7 +16,9 @@ see the COMBINED per-step distribution of its M members (1 ≤ M ≤ 8) instead 
   ``Translator`` decodes;
 - members must agree on ``AGREE`` (the batch structure, the score columns and the decoder's shapes); anything else may differ;
 - ``incremental=False`` and ``two_streams`` are not offered; ``self.model`` is member 0, which the plans read their shapes from;
-- ``graph=True`` replays the whole M-member decode as one graph; it is re-captured when any member's parameters move.
+- ``graph=True`` replays the whole M-member decode as one graph; it is re-captured when any member's parameters move;
+- the rule itself is one method, ``_combine`` (the decoder side and forced scoring both call it), and the clip features a member's
+  encoder side reads another, ``_member_features``: svpc_amd/contrast_decode.py overrides the two for contrastive decoding.
 
 tests/ensemble_reference.py restates the rule and the decodes on the CPU."""
 from __future__ import annotations
@@ -33,8 +35,8 @@ AGREE = ("model_mode", "vocab_size", "max_t_len", "max_v_len", "max_i_len", "vid
 class _EnsembleSide(object):
     """``_DecoderSide``'s surface over the M members' sides: caches and rows per member, one combined score matrix per iteration"""
 
-    def __init__(self, sides, weights, rule):
-        self.sides, self.weights, self.rule = sides, weights, rule
+    def __init__(self, sides, combine):
+        self.sides, self.combine = sides, combine                    # ``combine``: the translator's rule (``EnsembleTranslator._combine``)
         self.model, self.wide = sides[0].model, sides[0].wide        # (the loops read the config and the device from member 0)
         self.member_logits = sides[0].logits
         self.logits = False                                          # ``scores`` returns probabilities in every mode
@@ -55,8 +57,7 @@ class _EnsembleSide(object):
         L = self.n_layers
         mats = [s.scores(rows[m], ptr, nxt, i, caches[m * L:(m + 1) * L], seq_self, seq_cross, key_rows, group)
                 for m, s in enumerate(self.sides)]
-        return ops.ensemble_combine(mats, ptr["row_c"], weights=self.weights, rule=self.rule, logits=self.member_logits, unk=UNK,
-                                    max_cols=ptr["c_max"])
+        return self.combine(mats, ptr["row_c"], self.member_logits, 1, ptr["c_max"])
 
 
 class EnsembleTranslator(Translator):
@@ -69,6 +70,11 @@ class EnsembleTranslator(Translator):
         if combine not in ops.ENSEMBLE_RULES:
             raise ValueError("combine must be one of %s, got %r" % (", ".join(ops.ENSEMBLE_RULES), combine))
         self.combine = combine
+        self._adopt(opt, checkpoints, models, graph)
+
+    def _adopt(self, opt, checkpoints, models, graph):
+        """the members checked against ``AGREE`` and for one device, member 0 through ``Translator.__init__``, every further member
+        loaded and given its weight store"""
         first = checkpoints[0]["model_cfg"]
         for m, (ck, model) in enumerate(zip(checkpoints, models)):
             for cfg in (ck["model_cfg"], model.config):
@@ -78,7 +84,7 @@ class EnsembleTranslator(Translator):
         devs = {next(model.parameters()).device for model in models}
         if len(devs) != 1:
             raise ValueError("the members of an ensemble must be on one device, got %s" % ", ".join(sorted(str(d) for d in devs)))
-        super().__init__(opt, checkpoints[0], model=models[0], incremental=True, graph=graph)
+        Translator.__init__(self, opt, checkpoints[0], model=models[0], incremental=True, graph=graph)
         for ck, model in zip(checkpoints[1:], models[1:]):
             model.load_state_dict(ck["model"])
             model.eval()
@@ -103,26 +109,35 @@ class EnsembleTranslator(Translator):
     def _members(self):
         return self.models
 
+    def _combine(self, mats, row_c, logits, rows_per, max_cols):
+        """the members' score matrices of one step (or of a forced pass) → the ONE probability matrix the step kernels see: the seam a
+        subclass with another rule overrides (svpc_amd/contrast_decode.py)"""
+        return ops.ensemble_combine(mats, row_c, weights=self.weights, rule=self.combine, logits=logits, unk=UNK, rows_per=rows_per,
+                                    max_cols=max_cols)
+
+    def _member_features(self, k, feats):
+        """the clip features member k's encoder side reads: the batch's, for every member of an ensemble"""
+        return feats
+
     def _encode(self, model, dp, feats, ids_all, masks_all, ingr_ids_flat, cx):
         """every member's encoder side → [(model, its context, mem, bank)], member 0 with the decode's own context"""
         out = []
-        for m in self.models:
+        for k, m in enumerate(self.models):
             cxm = cx if m is model else _Ctx(m.config, False, m.rng(feats.device))
-            out.append((m, cxm) + tuple(self._encoder_side(m, dp, feats, ids_all, masks_all, ingr_ids_flat, cxm)))
+            out.append((m, cxm) + tuple(self._encoder_side(m, dp, self._member_features(k, feats), ids_all, masks_all, ingr_ids_flat, cxm)))
         return out
 
     def _side(self, model, dp, enc, cx):
         Lt = model.config.max_t_len
         return _EnsembleSide([_DecoderSide(m, cxm, mem, bank, self._text_table(m, Lt, cxm, mem.device), dp.T) for m, cxm, mem, bank in enc],
-                             self.weights, self.combine)
+                             self._combine)
 
     def _force(self, model, dp, enc, cx):
         """forced scoring: every member's (T·K·Lt, C) score matrix, combined (Lt rows per caption share its column count), scored as
         probabilities"""
         text, tmask, tgt, length, fin = self._force_inputs(model, dp)
         mats = [self._force_scores(m, dp, mem, bank, cxm, text, tmask) for m, cxm, mem, bank in enc]
-        scores = ops.ensemble_combine(mats, dp.cap_c, weights=self.weights, rule=self.combine, logits=model.config.model_mode == "video",
-                                      unk=UNK, rows_per=model.config.max_t_len, max_cols=max(dp.c_list))
+        scores = self._combine(mats, dp.cap_c, model.config.model_mode == "video", model.config.max_t_len, max(dp.c_list))
         if dp.raw:                                 # ``teacher_scores``: the combined matrix itself, probabilities in every mode
             return self._force_raw(model, dp, scores, False)
         return self._force_finish(model, dp, scores, tgt, length, fin, False)

@@ -2825,6 +2825,57 @@ def ensemble_combine(scores_list, row_c, *, weights, rule, logits, unk, rows_per
     return out
 
 
+def contrast_coefficients(expert_weight, amateur_weight, alpha, who="contrast_combine"):
+    """(we, wa, α, log α) as the kernel takes them: fp64, ``log α`` from ``math.log`` (−inf for α = 0).  ValueError for an expert weight
+    that is not finite or ≤ 0, an amateur weight that is not finite or < 0, and an α outside [0, 1] or NaN."""
+    try:
+        we, wa, al = float(expert_weight), float(amateur_weight), float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError("%s: expert_weight, amateur_weight and alpha must be numbers, got %r, %r, %r"
+                         % (who, expert_weight, amateur_weight, alpha))
+    if not (math.isfinite(we) and we > 0):
+        raise ValueError("%s: expert_weight must be finite and > 0, got %r" % (who, expert_weight))
+    if not (math.isfinite(wa) and wa >= 0):
+        raise ValueError("%s: amateur_weight must be finite and >= 0, got %r" % (who, amateur_weight))
+    if not 0.0 <= al <= 1.0:
+        raise ValueError("%s: alpha must lie in [0, 1], got %r" % (who, alpha))
+    return we, wa, al, (math.log(al) if al > 0 else -math.inf)
+
+
+def contrast_combine(expert, amateur, row_c, *, expert_weight, amateur_weight, alpha, logits, unk, rows_per=1, max_cols=None):
+    """Contrastive decoding's step rule (svpc_contrast_combine): an expert's score matrix held against an amateur's.
+    ``expert`` / ``amateur`` fp32 (n_rows, ≥ C) matrices with unit column stride (each its own row stride) — probabilities, or logits
+    when ``logits`` —, ``row_c`` the column counts (row r has C = row_c[r // rows_per] columns).  Over the head — the columns whose
+    expert probability is at least ``alpha`` times the row's highest, UNK never among them — out is the softmax of
+    ``expert_weight``·log p_expert − ``amateur_weight``·max(log p_amateur, log 1e-30); everything else is 0.  With
+    ``amateur_weight == 0`` the amateur's matrix is checked but never read.  → out (n_rows, max_c) fp32: a distribution over the head,
+    what the step kernels take with ``logits=False``.  The coefficients travel as kernel arguments: nothing is uploaded."""
+    we, wa, al, log_al = contrast_coefficients(expert_weight, amateur_weight, alpha)
+    ms = [expert, amateur]
+    for s in ms:
+        if not isinstance(s, torch.Tensor) or s.dim() != 2 or s.dtype != torch.float32 or (s.stride(1) != 1 and s.shape[1] != 1):
+            raise ValueError("contrast_combine: the expert's and the amateur's scores must be fp32 (rows, C) matrices with unit column stride")
+    n_rows, dev = expert.shape[0], expert.device
+    if amateur.shape[0] != n_rows or amateur.device != dev:
+        raise ValueError("contrast_combine: the two score matrices must have the same rows on the same device")
+    if int(rows_per) < 1:
+        raise ValueError("contrast_combine: rows_per must be >= 1")
+    rc = as_idx(row_c)
+    if len(rc) * int(rows_per) < n_rows:
+        raise ValueError("contrast_combine: %d column counts for %d rows (%d rows each)" % (len(rc), n_rows, rows_per))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if n_rows else 1)
+    if not 1 <= max_c <= SAMPLE_COLS_MAX or any(max_c > s.shape[1] for s in ms):
+        raise ValueError("contrast_combine: rows of 1..%d columns, inside both score matrices" % SAMPLE_COLS_MAX)
+    _need_gpu(expert)
+    out = torch.empty(n_rows, max_c, dtype=torch.float32, device=dev)
+    if n_rows == 0:
+        return out
+    _lib.call("contrast_combine", _p(expert), expert.stride(0), _p(amateur), amateur.stride(0), ctypes.c_double(we), ctypes.c_double(wa),
+              ctypes.c_double(al), ctypes.c_double(log_al), _p(rc.dev(dev)), int(rows_per), n_rows, max_c, 1 if logits else 0, int(unk),
+              _p(out), out.stride(0), _stream())
+    return out
+
+
 CAPTION_LT_MAX = 64             # a caption row: one lane per position
 CAPTION_VIDEO_WORDS = 4096      # positions (S_b · Lt) of one video's captions: the words live in the workgroup's LDS
 CAPTION_COUNT_COLS = 12         # total_1..4, distinct_1..4, n_sen, n_words, n_empty, n_copied
