@@ -610,6 +610,18 @@ int svpc_contrastive_step(const float* scores, int ld, const int* row_c, const i
 int svpc_sample_step(const float* scores, int ld, const int* row_c, const int* row_x, int n_rows, int max_c, int pos, int logits, int unk,
                      int eos, int pad, double temp, int topk, double topp, int min_len, const long long* seed, float* cum, int* finished,
                      int* len, int* text_out, int* ext_out, int ld_tok, int* next_ext, int* next_model, svpc_stream_t stream);
+/* svpc_sample_step with four further truncation stages between top-p and the draw, in this order, each off at 0 and each over the
+ * distribution renormalised over the survivors of the stage before it (first = the first survivor in candidate order, w = exp(z − z_first),
+ * q = w / Σ w, ln q = (z − z_first) − ln Σ w, all fp64): min_p in [0, 1) keeps w >= min_p; typical_p in [0, 1] (1: off) keeps the columns
+ * with |−ln q − H| <= d*, H the entropy, d* the smallest such distance whose columns hold typical_p of the mass (equal distances stay or go
+ * together; the mode may go); epsilon in [0, 1) keeps q >= epsilon; eta in [0, 1) keeps q >= min(eta, sqrt(eta)·exp(−H)); min-p, epsilon
+ * and eta always keep the first survivor.  The draw (same z, same hash index, same tie rule) is over what is left; cum adds the
+ * untruncated step score.  kept_out (n_rows, may be NULL): the size of the final set of each live row, 0 for a finished or empty row.
+ * All four at 0: the results of svpc_sample_step bit for bit. */
+int svpc_sample_step_trunc(const float* scores, int ld, const int* row_c, const int* row_x, int n_rows, int max_c, int pos, int logits,
+                           int unk, int eos, int pad, double temp, int topk, double topp, int min_len, const long long* seed, float* cum,
+                           int* finished, int* len, int* text_out, int* ext_out, int ld_tok, int* next_ext, int* next_model, double min_p,
+                           double typical_p, double epsilon, double eta, int* kept_out, svpc_stream_t stream);
 /* the seed of one sampling decode, on the device: src = (fixed, value); fixed != 0: *used = value; otherwise *used is drawn from the
  * decode's seed word *word, which advances (consecutive replays of one captured decode draw different streams) */
 int svpc_sample_seed(const long long* src, long long* word, long long* used, svpc_stream_t stream);

@@ -2718,6 +2718,50 @@ def check_sampling(lt, num_samples=1, random_sampling_temp=1.0, random_sampling_
     return dict(num_samples=R, random_sampling_temp=temp, random_sampling_topk=max(k, 0), random_sampling_topp=q, min_length=m, seed=seed)
 
 
+def check_truncation(min_p=0.0, typical_p=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0):
+    """The truncation settings of a sampling decode, checked on the host (ValueError for a non-number, a bool, NaN or a value out of
+    range) and normalised → dict(min_p a (in [0, 1); 0: off), typical_p m (in [0, 1]; 0 and 1: off, 1 is returned as 0), epsilon_cutoff ε
+    and eta_cutoff η (in [0, 1); 0: off)), all floats."""
+    out = {}
+    for name, v, closed in (("min_p", min_p, False), ("typical_p", typical_p, True), ("epsilon_cutoff", epsilon_cutoff, False),
+                            ("eta_cutoff", eta_cutoff, False)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        f = float(v)
+        if not (0.0 <= f <= 1.0 if closed else 0.0 <= f < 1.0):          # (NaN fails too)
+            raise ValueError("%s must be in [0, 1%s, got %r" % (name, "]" if closed else ")", v))
+        out[name] = f + 0.0                                               # (−0.0 → 0.0)
+    if out["typical_p"] == 1.0:
+        out["typical_p"] = 0.0
+    return out
+
+
+def _sample_step_checks(name, scores, row_c, cum, finished, length, text, ext, seed, pos, temp, topk, topp, min_length, max_cols):
+    """the checks ``sample_step`` and ``sample_step_trunc`` share → (rows, Lt, the row_c index, max(row_c))"""
+    R = cum.shape[0]
+    if scores.dim() != 2 or scores.shape[0] != R or scores.stride(1) != 1 or scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be fp32 (T·R, C) rows with unit column stride" % name)
+    for t, dt in ((cum, torch.float32), (finished, torch.int32), (length, torch.int32)):
+        if not _row_vec(t, R, dt, scores.device):
+            raise ValueError("%s: cum fp32, finished and length int32, all contiguous (T·R,) on the scores' device" % name)
+    lt = text.shape[1]
+    for m in (text, ext):
+        if not _id_rows(m, R, lt, scores.device):
+            raise ValueError("%s: id matrices must be contiguous int32 (T·R, Lt) on the scores' device" % name)
+    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
+        raise ValueError("%s: seed must be a device int64 tensor" % name)
+    if not 0 <= pos < lt - 1:
+        raise ValueError("%s: position %d outside the %d-column matrices" % (name, pos, lt))
+    if not (math.isfinite(temp) and temp > 0 and topk >= 0 and 0.0 <= topp <= 1.0 and 0 <= min_length < lt):
+        raise ValueError("%s: temp finite > 0, topk >= 0, topp in [0, 1], min_length 0..Lt-1" % name)
+    rc = as_idx(row_c)
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > SAMPLE_COLS_MAX or max_c > scores.shape[1]:
+        raise ValueError("%s: rows of at most %d columns, inside the score matrix" % (name, SAMPLE_COLS_MAX))
+    _need_gpu(scores)
+    return R, lt, rc, max_c
+
+
 def sample_step(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished, length, text, ext, seed, *, temp=1.0, topk=0, topp=0.0,
                 min_length=0, max_cols=None):
     """One random-sampling step (svpc_sample_step) over ``scores`` (T·R, ≥ C) — probabilities, or logits when ``logits``: every row draws
@@ -2726,27 +2770,8 @@ def sample_step(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished,
     whatever it holds).  ``cum`` fp32, ``finished`` / ``length`` int32 (T·R,) are updated in place, and column pos + 1 of the (T·R, Lt)
     int32 id matrices ``text`` / ``ext``.  ``max_cols``: max(row_c) when the caller knows it (else taken from the host copy).
     → (next_ext, next_model) int32 (T·R,)."""
-    R = cum.shape[0]
-    if scores.dim() != 2 or scores.shape[0] != R or scores.stride(1) != 1 or scores.dtype != torch.float32:
-        raise ValueError("sample_step: scores must be fp32 (T·R, C) rows with unit column stride")
-    for t, dt in ((cum, torch.float32), (finished, torch.int32), (length, torch.int32)):
-        if not _row_vec(t, R, dt, scores.device):
-            raise ValueError("sample_step: cum fp32, finished and length int32, all contiguous (T·R,) on the scores' device")
-    lt = text.shape[1]
-    for m in (text, ext):
-        if not _id_rows(m, R, lt, scores.device):
-            raise ValueError("sample_step: id matrices must be contiguous int32 (T·R, Lt) on the scores' device")
-    if seed.dtype != torch.int64 or seed.numel() < 1 or seed.device != scores.device:
-        raise ValueError("sample_step: seed must be a device int64 tensor")
-    if not 0 <= pos < lt - 1:
-        raise ValueError("sample_step: position %d outside the %d-column matrices" % (pos, lt))
-    if not (math.isfinite(temp) and temp > 0 and topk >= 0 and 0.0 <= topp <= 1.0 and 0 <= min_length < lt):
-        raise ValueError("sample_step: temp finite > 0, topk >= 0, topp in [0, 1], min_length 0..Lt-1")
-    rc = as_idx(row_c)
-    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
-    if max_c > SAMPLE_COLS_MAX or max_c > scores.shape[1]:
-        raise ValueError("sample_step: rows of at most %d columns, inside the score matrix" % SAMPLE_COLS_MAX)
-    _need_gpu(scores)
+    R, lt, rc, max_c = _sample_step_checks("sample_step", scores, row_c, cum, finished, length, text, ext, seed, pos, temp, topk, topp,
+                                           min_length, max_cols)
     dev = scores.device
     nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
     nxt = torch.empty(R, dtype=torch.int32, device=dev)
@@ -2754,6 +2779,30 @@ def sample_step(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished,
               1 if logits else 0, int(unk), int(eos), int(pad), float(temp), int(topk), float(topp), int(min_length), _p(seed), _p(cum),
               _p(finished), _p(length), _p(text), _p(ext), lt, _p(nxt_ext), _p(nxt), _stream())
     return nxt_ext, nxt
+
+
+def sample_step_trunc(scores, row_c, row_x, pos, logits, unk, eos, pad, cum, finished, length, text, ext, seed, *, temp=1.0, topk=0,
+                      topp=0.0, min_length=0, max_cols=None, min_p=0.0, typical_p=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0, kept=None):
+    """``sample_step`` with the four truncation stages of ``check_truncation`` between top-p and the draw (svpc_sample_step_trunc; min-p,
+    locally typical, epsilon and eta, in this order, each off at 0, each over the distribution renormalised over what the stage before
+    left).  Everything else — arguments, checks, what is updated in place — is ``sample_step``'s; with all four off so are the results,
+    bit for bit.  → (next_ext, next_model, kept) int32 (T·R,): ``kept`` is the size of the set each live row drew from (0 for a
+    finished row or one without candidates), written into ``kept`` when the caller brings one."""
+    R, lt, rc, max_c = _sample_step_checks("sample_step_trunc", scores, row_c, cum, finished, length, text, ext, seed, pos, temp, topk,
+                                           topp, min_length, max_cols)
+    tr = check_truncation(min_p, typical_p, epsilon_cutoff, eta_cutoff)
+    dev = scores.device
+    nxt_ext = torch.empty(R, dtype=torch.int32, device=dev)
+    nxt = torch.empty(R, dtype=torch.int32, device=dev)
+    if kept is None:
+        kept = torch.empty(R, dtype=torch.int32, device=dev)
+    elif not _row_vec(kept, R, torch.int32, dev):
+        raise ValueError("sample_step_trunc: kept must be a contiguous int32 (T·R,) tensor on the scores' device")
+    _lib.call("sample_step_trunc", _p(scores), scores.stride(0), _p(rc.dev(dev)), _p(as_idx(row_x).dev(dev)), R, int(max_c), int(pos),
+              1 if logits else 0, int(unk), int(eos), int(pad), float(temp), int(topk), float(topp), int(min_length), _p(seed), _p(cum),
+              _p(finished), _p(length), _p(text), _p(ext), lt, _p(nxt_ext), _p(nxt), tr["min_p"], tr["typical_p"], tr["epsilon_cutoff"],
+              tr["eta_cutoff"], _p(kept), _stream())
+    return nxt_ext, nxt, kept
 
 
 def sample_seed(src, word, used):

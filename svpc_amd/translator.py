@@ -98,6 +98,18 @@ and ``ops.beam_step`` keeps a per-hypothesis ancestry table of cache rows that t
 - every argument is checked on the host before any device work: ValueError for R, τ (finite > 0), k (≥ −1), q ([0, 1]), m (0 … Lt − 1),
   the seed, and rows wider than 4096 columns; TypeError for an unknown keyword; ``incremental=False`` raises NotImplementedError.
   Each setting (R, τ, k, q, m) has its own prepared plan and captured graph; the seed is a captured input.
+- truncation: four further keywords, each off at 0, also read from ``opt`` — ``min_p`` a ∈ [0, 1) (Nguyen et al. 2024),
+  ``typical_p`` m ∈ [0, 1] (locally typical sampling, Meister et al. 2022; 1 is off too), ``epsilon_cutoff`` ε and ``eta_cutoff`` η ∈
+  [0, 1) (Hewitt et al. 2022).  They run in this order on K2, every stage over the distribution renormalised over the survivors of the
+  one before (first = their ≻-first column, w_c = exp(z_c − z_first), W = Σ w, q_c = w_c / W, ln q_c = (z_c − z_first) − ln W, fp64):
+  min-p keeps w_c ≥ a; typical keeps d_c = |−ln q_c − H| ≤ d*, H = −Σ q ln q, d* the smallest d whose columns {d_c ≤ d*} hold m of the
+  mass (equal d stay or go together; the mode may go; never empty); epsilon keeps q_c ≥ ε; eta keeps q_c ≥ min(η, √η·exp(−H)); min-p,
+  epsilon and eta always keep the first column.  The pick is the same Gumbel-max (same z, same hash index, same tie rule) over what is
+  left, and cum still adds the model's untruncated step score, so ``score_captions`` reproduces it.  ValueError for a non-number, a
+  bool, NaN or a value out of range.  With all four off the decode is the one above — the same plan, the same launches, the same ids
+  bit for bit; otherwise the setting joins the plan key, the selection is ``ops.sample_step_trunc``, and ``last_sample_kept`` holds
+  the (Lt − 1, T·R) int32 sizes of the sets the rows drew from (0 once finished).  ``translate_batch_stochastic`` rejects the four
+  keywords (TypeError): truncation would break its sampling without replacement.
 
 **Captions from ids** (the reference's host tail, src/translate.py:81-83): ``Translator.clean_captions(dec_seq_list, row=0,
 remove_dup=True)`` turns any of the results above into the clean captions on the device (the ids without PAD / IGNORE, without the first
@@ -273,15 +285,19 @@ class Decode(object):
     captured input, like ``given``); only the fact that the decode is constrained is part of the key.
     Stochastic beam search: BEAM with ``stochastic`` = (τ, m) — part of the key — and ``seed`` as sampling's.
     Contrastive search: BEAM with ``contrastive`` = (k, fp32 α, m) — part of the key: α is baked into a captured graph, so two α never
-    share one."""
-    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons", "stochastic", "contrastive")
+    share one.
+    Truncated sampling: SAMPLE with ``truncation`` = (min_p, typical_p, epsilon_cutoff, eta_cutoff), None when all four are off — part
+    of the key only then, so a plain sampling decode keeps its key."""
+    __slots__ = ("kind", "width", "controls", "ctl_key", "n_best", "sampling", "seed", "given", "groups", "cons", "stochastic", "contrastive",
+                 "truncation")
 
     def __init__(self, kind=GREEDY, width=1, controls=None, ctl_key=None, n_best=0, sampling=None, seed=None, given=None, groups=None,
-                 cons=None, stochastic=None, contrastive=None):
+                 cons=None, stochastic=None, contrastive=None, truncation=None):
         self.kind, self.width, self.controls, self.ctl_key, self.n_best, self.sampling, self.seed, self.given, self.groups, self.cons = (
             kind, width, controls, ctl_key, n_best, sampling, seed, given, groups, cons)
         self.stochastic = stochastic
         self.contrastive = contrastive
+        self.truncation = truncation
 
     @property
     def constrained(self):
@@ -296,7 +312,8 @@ class Decode(object):
     def key(self):
         return ((self.kind, self.width, self.ctl_key, self.ranked, self.sampling) + ((self.groups,) if self.groups is not None else ())
                 + (("constrained",) if self.constrained else ()) + ((("stochastic",) + tuple(self.stochastic),) if self.stochastic is not None else ())
-                + ((("contrastive",) + tuple(self.contrastive),) if self.contrastive is not None else ()))
+                + ((("contrastive",) + tuple(self.contrastive),) if self.contrastive is not None else ())
+                + ((("truncation",) + tuple(self.truncation),) if self.truncation is not None else ()))
 
 
 class DecodePlan(object):
@@ -311,6 +328,7 @@ class DecodePlan(object):
                  "groups", "pen",                               # diverse beam search: G, the device penalty table (ops.diversity_table)
                  "cons",                                        # constrained beam search: the (T, 4, 4) device table, a captured input
                  "sampling", "key_rows", "seed_src", "seed_used",       # sampling: ops.sample_step's keywords, ancestry, seed words
+                 "truncation", "kept",                          # truncated sampling: ops.sample_step_trunc's further keywords, kept (Lt − 1, T·R)
                  "stochastic",                                  # stochastic beam search: ops.stochastic_beam_step's keywords (+ the seed words)
                  "contrastive",                                 # contrastive search: ops.contrastive_step's keywords
                  "given", "unk", "ptr_force", "cap_c", "force_self", "force_cross", "group_rows",     # forced scoring (``_force_pass``)
@@ -401,6 +419,7 @@ class Translator(object):
         self._ttab = {}             # id(model) → (key, the per-checkpoint text-embedding table): see _text_table
         self._seed_word = None      # sampling with seed=None: the device-resident seed word the decode advances (see translate_batch_sample)
         self.last_sample_seed = None
+        self.last_sample_kept = None    # truncated sampling: the last decode's kept-set sizes (Lt − 1, T·R) int32, 0 for finished rows
         self.device = torch.device("cuda" if getattr(opt, "cuda", True) else "cpu")
         self.model_config = checkpoint["model_cfg"]
         self.max_t_len = self.model_config.max_t_len
@@ -551,21 +570,25 @@ class Translator(object):
         return out
 
     SAMPLING = dict(random_sampling_temp=1.0, random_sampling_topk=0, random_sampling_topp=0.0, min_length=0)
+    TRUNCATION = dict(min_p=0.0, typical_p=0.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
 
     @torch.no_grad()
     def translate_batch_sample(self, model_inputs, num_samples=1, seed=None, **kw):
         """``num_samples`` random samples per sentence (module docstring) → (dec_seq_list, oov_word_dict, score_list, length_list): per
         video ids (S_b, R, Lt) int64, cum (S_b, R) fp32 and len (S_b, R) int64, in sample order."""
-        unknown = set(kw) - set(self.SAMPLING)
+        unknown = set(kw) - set(self.SAMPLING) - set(self.TRUNCATION)
         if unknown:
             raise TypeError("unknown sampling keyword(s): %s" % ", ".join(sorted(unknown)))
         val = {k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.SAMPLING.items()}
         s = check_sampling(self.max_t_len, num_samples=num_samples, seed=seed, max_cols=self._max_cols(model_inputs), **val)
+        tr = ops.check_truncation(**{k: kw[k] if k in kw else getattr(self.opt, k, d) for k, d in self.TRUNCATION.items()})
         if not self.incremental:
             raise NotImplementedError("sampling decodes incrementally only (Translator(incremental=True))")
         R = s["num_samples"]
-        return self._translate(model_inputs, self.model, decode=Decode(SAMPLE, R, n_best=R, seed=s["seed"], sampling=tuple(
-            s[k] for k in ("random_sampling_temp", "random_sampling_topk", "random_sampling_topp", "min_length"))))
+        return self._translate(model_inputs, self.model, decode=Decode(
+            SAMPLE, R, n_best=R, seed=s["seed"],
+            sampling=tuple(s[k] for k in ("random_sampling_temp", "random_sampling_topk", "random_sampling_topp", "min_length")),
+            truncation=tuple(tr[k] for k in self.TRUNCATION) if any(tr.values()) else None))
 
     STOCHASTIC = dict(random_sampling_temp=1.0, min_length=0)
 
@@ -819,6 +842,9 @@ class Translator(object):
             dp.key_rows = (torch.arange(T * W, dtype=torch.int32, device=dev).unsqueeze(1) * Lt +
                            torch.arange(Lt, dtype=torch.int32, device=dev)).contiguous()
             dp.seed_src, dp.seed_used = torch.zeros(2, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+            if decode.truncation is not None:      # every step's kept-set sizes: a buffer of the plan, so a replayed graph fills it again
+                dp.truncation = dict(zip(self.TRUNCATION, decode.truncation))
+                dp.kept = torch.zeros(Lt - 1, T * W, dtype=torch.int32, device=dev)
         if decode.stochastic is not None:      # the seed source and the seed the decode used: captured device words, as sampling's
             temp, m = decode.stochastic
             dp.stochastic = dict(temp=temp, min_length=m, max_cols=dp.ptr_hyp["c_max"])
@@ -1183,8 +1209,12 @@ class Translator(object):
         caches, rows, seq_self, seq_cross = side.caches(n), side.rows(), self._self_segs(dp, Lt, dev), side.seq_cross(dp)
         for i in range(Lt - 1):
             scores = side.scores(rows, dp.ptr_hyp, nxt, i, caches, seq_self[i], seq_cross, dp.key_rows, R)
-            _, nxt = ops.sample_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, side.logits, UNK, EOS, PAD, cum, fin, length,
-                                     text, ext, dp.seed_used, **dp.sampling)
+            if dp.truncation is None:
+                _, nxt = ops.sample_step(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, side.logits, UNK, EOS, PAD, cum, fin, length,
+                                         text, ext, dp.seed_used, **dp.sampling)
+            else:
+                _, nxt, _ = ops.sample_step_trunc(scores, dp.ptr_hyp["row_c"], dp.x_hyp, i, side.logits, UNK, EOS, PAD, cum, fin, length,
+                                                  text, ext, dp.seed_used, kept=dp.kept[i], **dp.sampling, **dp.truncation)
         return ext.view(T, R, Lt), cum.view(T, R), length.view(T, R)
 
     @staticmethod
@@ -1289,6 +1319,8 @@ class Translator(object):
                 out = self._decode_graphed(model, dp, src, (S_pad, n, L, F), stream)
             if dp.seed_used is not None:
                 self.last_sample_seed = dp.seed_used.clone()
+            if decode.kind == SAMPLE:         # (the plan's own buffer, not a copy: the next decode of this setting fills it again)
+                self.last_sample_kept = dp.kept
             return dp.plan, out
 
         # Two halves on two streams: the encoder side of a batch is bound by the matrix cores, the Lt decoding

@@ -102,7 +102,7 @@ class Unlikelihood(object):
         if source not in SOURCES:
             raise ValueError("source must be one of %s, got %r" % (", ".join(SOURCES), source))
         tr = self.translator
-        unknown = set(sampling_kw) - set(tr.SAMPLING)
+        unknown = set(sampling_kw) - set(tr.SAMPLING) - set(tr.TRUNCATION)
         if unknown:
             raise TypeError("unknown keyword(s): %s" % ", ".join(sorted(unknown)))
         model = tr.model
