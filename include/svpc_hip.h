@@ -873,6 +873,29 @@ int svpc_seq_risk_fwd(const float* scores, int ld, const int* row_c, int max_c, 
                       double length_beta, double margin, double risk_weight, double rank_weight, float* step, float* cum, int* barred,
                       double* risk, double* rank, double* q, double* z, int* valid, float* w_eff, float* loss, svpc_stream_t stream);
 
+/* ---- preference optimisation over a video's k candidate paragraphs against a frozen reference model (DPO, cDPO, IPO, SLiC's
+ *      hinge, SimPO).  Layout, tgt / len / row_w / cost / vid_off as minimum-risk training above; ref_cum (n_cap,) fp32 the reference
+ *      model's cum of the same captions, or NULL (reference-free: the bits of an all-zero ref_cum).  In fp64, per video and candidate:
+ *      s / s_ref = the sums of cum / ref_cum over the video's sentences in order, n = max(1, the sum of len); valid = no sentence barred,
+ *      every ref_cum finite and a finite cost; u = (s − s_ref) / n^length_beta (0 when invalid); pos = the valid candidates before this one
+ *      by (cost, c); the pairs (i, j) of valid candidates: pairs 0 ("all") every cost_i < cost_j, 1 ("extremes") pos_i = 0 and pos_j = the
+ *      valid count − 1 with cost_i < cost_j; d = u_i − u_j, h = beta·d − gamma; the pair's loss l: loss_type 0 (sigmoid) −(1 −
+ *      label_smoothing)·ln s(h) − label_smoothing·ln s(−h) with ln s(x) = min(x, 0) − log1p(exp(−|x|)), 1 (hinge) max(0, 1 − h), 2 (ipo)
+ *      (d − 1 / (2 beta))²; D = dl / dd; G = (pref_weight / P)·(the sum of D over the pairs with c as i − over the pairs with c as j), P the
+ *      video's pairs; an invalid candidate stands in no pair and has G = 0. */
+/* step / cum / barred are svpc_seq_nll_fwd's (it is called: the same bits); pref (n_vid,) fp64 = the mean of l over the video's pairs (per
+ * i the sum over j ascending, then over i ascending), reward (n_vid, k) fp64 = beta·u, valid (n_vid, k) int32, n_pairs / n_correct (n_vid,)
+ * int32 = P and the pairs with d > 0, margin (n_vid,) fp64 = the mean of beta·d over the pairs — pref and margin 0 with no pair —, w_eff
+ * (n_cap,) = fp32(row_w − G / (n_vid·n^length_beta)) — every element written —; loss (1,) = fp32(−sum row_w·cum over the captions not barred
+ * + pref_weight·sum pref / n_vid), each sum in svpc_seq_nll_fwd's order (pref_weight 0: its bits, the second term not added).  The gradient
+ * is svpc_seq_nll_bwd under w_eff.  1 <= k <= 16; beta > 0; gamma, length_beta, pref_weight >= 0; 0 <= label_smoothing < 0.5 and 0 outside
+ * loss_type 0; gamma 0 under loss_type 2; all finite.  Five launches. */
+int svpc_seq_pref_fwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const float* row_w,
+                      const double* cost, const float* ref_cum, const int* vid_off, int n_vid, int n_sent, int k, int lt, int logits, int unk,
+                      double beta, double gamma, double label_smoothing, double length_beta, double pref_weight, int loss_type, int pairs,
+                      float* step, float* cum, int* barred, double* pref, double* reward, int* valid, int* n_pairs, int* n_correct,
+                      double* margin, float* w_eff, float* loss, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

@@ -3998,3 +3998,134 @@ def seq_risk(scores, row_c, tgt, length, cost, vid_off, row_w, logits, unk_id, a
     params = tuple(float(v) for v in (alpha, length_beta, margin, risk_weight, rank_weight))
     return _SeqRisk.apply(_c(scores), rc.dev(scores.device) if R else None, tgt, length, _c(cost), off.dev(scores.device), row_w,
                           1 if logits else 0, int(unk_id), max_c, params)
+
+
+# ------------------------------------------------------------------------------------------------ preference optimisation
+PREF_MAX = RISK_MAX             # candidates per sentence: one lane each (svpc_seq_pref_fwd)
+PREF_LOSS_TYPES = ("sigmoid", "hinge", "ipo")
+PREF_PAIRS = ("all", "extremes")
+
+
+def check_pref(k=None, cost=None, vid_off=None, n_sent=None, ref_cum=None, rows=None, beta=None, gamma=None, label_smoothing=None,
+               length_beta=None, pref_weight=None, loss_type=None, pairs=None, source=None, utility=None, device=None):
+    """Host checks of preference optimisation (ValueError for each): ``k`` / ``cost`` / ``vid_off`` / ``n_sent`` /
+    ``source`` / ``utility`` as ``check_risk`` takes them; ``beta`` finite and > 0; ``gamma``, ``length_beta`` and ``pref_weight`` finite
+    and not negative; ``label_smoothing`` in [0, 0.5) and 0 outside ``loss_type`` "sigmoid"; ``gamma`` 0 under "ipo"; ``loss_type`` one of
+    sigmoid / hinge / ipo; ``pairs`` one of all / extremes; ``ref_cum`` a contiguous fp32 tensor of ``rows`` elements (on ``device``, when
+    given).  ``SvpcKernelError`` for a cost or a ref_cum that is not on the GPU (no CPU fallback exists).  → (K, N, the utility's column
+    or None, the loss type's index or None, the pair mode's index or None)."""
+    if beta is not None and (isinstance(beta, bool) or not isinstance(beta, numbers.Real) or not math.isfinite(beta) or beta <= 0):
+        raise ValueError("beta must be a finite number > 0, got %r" % (beta,))
+    for name, v in (("gamma", gamma), ("length_beta", length_beta), ("pref_weight", pref_weight)):
+        _risk_number(name, v)
+    if label_smoothing is not None and (isinstance(label_smoothing, bool) or not isinstance(label_smoothing, numbers.Real)
+                                        or not 0 <= label_smoothing < 0.5):
+        raise ValueError("label_smoothing must lie in [0, 0.5), got %r" % (label_smoothing,))
+    if loss_type is not None and loss_type not in PREF_LOSS_TYPES:
+        raise ValueError("loss_type must be one of %s, got %r" % (", ".join(PREF_LOSS_TYPES), loss_type))
+    if pairs is not None and pairs not in PREF_PAIRS:
+        raise ValueError("pairs must be one of %s, got %r" % (", ".join(PREF_PAIRS), pairs))
+    kind = loss_type if loss_type is not None else "sigmoid"
+    if label_smoothing and kind != "sigmoid":
+        raise ValueError("label_smoothing belongs to the sigmoid loss, got %r with loss_type %r" % (label_smoothing, kind))
+    if gamma and kind == "ipo":
+        raise ValueError("the ipo loss takes no gamma, got %r" % (gamma,))
+    if ref_cum is not None:
+        if (not torch.is_tensor(ref_cum) or ref_cum.dtype != torch.float32 or not ref_cum.is_contiguous()
+                or (rows is not None and ref_cum.numel() != rows)):
+            raise ValueError("ref_cum must be contiguous fp32 of %s elements (one per caption row), got %s"
+                             % (rows, "%s %s" % (tuple(ref_cum.shape), ref_cum.dtype) if torch.is_tensor(ref_cum) else type(ref_cum).__name__))
+        if device is not None and ref_cum.device != device:
+            raise ValueError("ref_cum must be on the scores' device %s, got %s" % (device, ref_cum.device))
+    K, N, col = check_risk(k=k, cost=cost, vid_off=vid_off, n_sent=n_sent, source=source, utility=utility, device=device)
+    if ref_cum is not None and not ref_cum.is_cuda:
+        raise _lib.SvpcKernelError("svpc_amd.ops: preference optimisation runs on the GPU only (no CPU fallback exists)")
+    return (K, N, col, None if loss_type is None else PREF_LOSS_TYPES.index(loss_type), None if pairs is None else PREF_PAIRS.index(pairs))
+
+
+class _SeqPref(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, cost, off, ref_cum, row_w, logits, unk_id, max_c, params, kinds):
+        R, lt = tgt.shape
+        N, K = cost.shape
+        dev = scores.device
+        step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        cum = torch.empty(R, dtype=torch.float32, device=dev)
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        pref = torch.empty(N, dtype=torch.float64, device=dev)
+        reward = torch.empty(N, K, dtype=torch.float64, device=dev)
+        valid = torch.empty(N, K, dtype=torch.int32, device=dev)
+        n_pairs = torch.empty(N, dtype=torch.int32, device=dev)
+        n_correct = torch.empty(N, dtype=torch.int32, device=dev)
+        margin = torch.empty(N, dtype=torch.float64, device=dev)
+        w_eff = torch.empty(R, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_pref_fwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(row_w), _p(cost), _p(ref_cum), _p(off),
+                  N, R // K, K, lt, logits, unk_id, *params, *kinds, _p(step), _p(cum), _p(barred), _p(pref), _p(reward), _p(valid),
+                  _p(n_pairs), _p(n_correct), _p(margin), _p(w_eff), _p(loss), _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, w_eff)
+        ctx.cfg = (R, lt, logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred, pref, reward, valid, n_pairs, n_correct, margin, w_eff)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred, pref, reward, valid, n_pairs, n_correct, margin, w_eff
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 13
+        scores, rc, tgt, length, barred, w_eff = ctx.saved_tensors
+        R, lt, logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        # the objective's derivative in cum is −w_eff: the gradient is seq_nll's under the effective weights, bit for bit
+        _lib.call("seq_nll_bwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(w_eff), _p(dl), R, lt,
+                  logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return (dscores,) + (None,) * 12
+
+
+def seq_pref(scores, row_c, tgt, length, cost, vid_off, ref_cum, row_w, logits, unk_id, beta, gamma, label_smoothing, length_beta,
+             pref_weight, loss_type, pairs, max_cols=None):
+    """``seq_nll`` plus the preference term over every video's K candidate paragraphs (svpc_seq_pref_fwd, and svpc_seq_nll_bwd under the
+    effective weights), differentiable in ``scores`` only: caption row r = t·K + k, ``cost`` (N, K) float64 the candidates'
+    costs (lower is preferred; a non-finite cost takes its candidate out), ``vid_off`` as ``seq_risk`` takes it, ``ref_cum`` (R,) fp32 the
+    frozen reference model's ``cum`` of the same captions (a non-finite entry takes its candidate out; None: reference-free, the bits of
+    an all-zero ``ref_cum``), ``row_w`` (R,) fp32 the captions' likelihood weights (None: zeros), the rest as ``seq_nll`` takes it.  u =
+    (Σ_t cum − Σ_t ref_cum) / (Σ_t len)^``length_beta``; over the pairs (i, j) of valid candidates with cost_i < cost_j (``pairs`` "all")
+    or the best against the worst (``"extremes"``): d = u_i − u_j, h = ``beta``·d − ``gamma``, ℓ = −(1 − ε)·ln σ(h) − ε·ln σ(−h)
+    (``loss_type`` "sigmoid", ε = ``label_smoothing``), max(0, 1 − h) ("hinge") or (d − 1 / (2·beta))² ("ipo"); pref[b] = the mean of ℓ over
+    the video's pairs.  → (loss () fp32 = −Σ w_r·cum_r + ``pref_weight``·Σ_b pref / N, cum, step, barred as ``seq_nll`` returns them — the
+    same bits —, pref (N,) float64, reward (N, K) float64 = beta·u the implicit reward, valid (N, K) int32, n_pairs / n_correct (N,) int32
+    (the pairs, and those with d > 0), margin (N,) float64 = the mean of beta·d over the pairs, w_eff (R,) fp32: the weights under which
+    ``seq_nll``'s gradient is this loss's).  With ``pref_weight`` = 0 the loss and its gradient have ``seq_nll``'s bits."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_pref: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_pref: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_pref: length must be contiguous int32 (R,) on the scores' device")
+    K, N, _, kind, mode = check_pref(cost=cost, ref_cum=ref_cum, rows=R, beta=beta, gamma=gamma, label_smoothing=label_smoothing,
+                                     length_beta=length_beta, pref_weight=pref_weight, loss_type=loss_type, pairs=pairs,
+                                     device=scores.device)
+    if kind is None or mode is None:
+        raise ValueError("seq_pref: loss_type must be one of %s and pairs one of %s" % (", ".join(PREF_LOSS_TYPES), ", ".join(PREF_PAIRS)))
+    if R % K:
+        raise ValueError("seq_pref: %d caption rows are no multiple of the K = %d candidates per sentence" % (R, K))
+    off = as_idx(vid_off)
+    check_risk(cost=cost, vid_off=off, n_sent=R // K)
+    if row_w is None:
+        row_w = torch.zeros(R, dtype=torch.float32, device=scores.device)
+    elif not torch.is_tensor(row_w) or not _row_vec(row_w, R, torch.float32, scores.device):
+        raise ValueError("seq_pref: row_w must be contiguous fp32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_pref: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_pref: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    _need_gpu(scores)
+    params = tuple(float(v) for v in (beta, gamma, label_smoothing, length_beta, pref_weight))
+    return _SeqPref.apply(_c(scores), rc.dev(scores.device) if R else None, tgt, length, _c(cost), off.dev(scores.device), ref_cum, row_w,
+                          1 if logits else 0, int(unk_id), max_c, params, (kind, mode))
