@@ -896,6 +896,43 @@ int svpc_seq_pref_fwd(const float* scores, int ld, const int* row_c, int max_c, 
                       float* step, float* cum, int* barred, double* pref, double* reward, int* valid, int* n_pairs, int* n_correct,
                       double* margin, float* w_eff, float* loss, svpc_stream_t stream);
 
+/* ---- clipped policy-gradient training over a video's k candidate paragraphs with a per-token KL against a frozen reference model
+ *      (PPO's clipped surrogate in its group form GRPO; DAPO and Dr. GRPO are settings).  Layout, tgt / len / row_w / vid_off as
+ *      preference optimisation above; adv (n_vid, k) fp64 the candidates' advantages; old_step / ref_step (n_cap, lt − 1) fp32 the behaviour
+ *      policy's and the reference model's step scores of the same captions, or NULL (no old_step: the ratio is exactly 1; no ref_step: no KL
+ *      term, kl_beta must be 0).  Per candidate: n = max(1, the sum of len over its sentences); valid = no sentence barred, a finite adv
+ *      and every old_step / ref_step entry at its scored positions (i < len) finite.  In fp64, per scored position of a valid candidate:
+ *      r = exp(step − old_step), A = adv; sur = min(r·A, clamp(r, 1 − clip_lo, 1 + clip_hi)·A), under dual_clip = c (0: off) and A < 0
+ *      sur = max(sur, c·A), A = 0: sur = 0; active = sur is the unclipped r·A (strict comparisons: an r on a bound is active); d = ref_step −
+ *      step, kl = exp(d) − d − 1; tok = −sur + kl_beta·kl; den = n_vid·k·n (norm 0, "sequence"), max(1, n_tok) (norm 1, "token") or n_vid·k
+ *      (norm 2, "none"); g = −A·r·[active] + kl_beta·(1 − exp(d)). */
+/* step / cum / barred are svpc_seq_nll_fwd's (it is called: the same bits); pos_w (n_cap, lt − 1) = fp32(row_w − g / den) at the scored
+ * positions of a valid candidate, row_w at those of any other candidate, 0 past a caption's end; pg / kl (n_cap,) fp64 = the row's sums of
+ * −sur and kl, n_clip (n_cap, 2) int32 = its positions clipped from above (r > 1 + clip_hi with A > 0, or r > c with A < 0) / from below
+ * (r < 1 − clip_lo with A < 0), ratio_max (n_cap,) fp32 = its largest r (0 with none), valid (n_vid, k) int32, n_tok (1,) int32 = the
+ * scored positions of all valid candidates; row_adv (n_cap,) fp64, row_n (n_cap,) int32 and row_tok (n_cap,) fp64 are the launches' own
+ * tables (the row's candidate's A and n, 0 when it is not valid, and the row's sum of tok / den) — every element of every output written,
+ * given a vid_off that covers the n_sent sentences —; loss (1,) = fp32(−sum row_w·cum over the captions not barred + sum row_tok), each
+ * sum in svpc_seq_nll_fwd's order (kl_beta 0 and no valid candidate's A different from 0: its bits, the second term not added).  The
+ * gradient is svpc_seq_pos_bwd under pos_w with dead = barred.  1 <= k <= 16; 0 <= clip_lo < 1; clip_hi, kl_beta >= 0; dual_clip 0 or
+ * > 1; all finite.  No atomics.  Seven launches. */
+int svpc_seq_pg_fwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const float* row_w,
+                    const double* adv, const float* old_step, const float* ref_step, const int* vid_off, int n_vid, int n_sent, int k, int lt,
+                    int logits, int unk, double clip_lo, double clip_hi, double dual_clip, double kl_beta, int norm, float* step, float* cum,
+                    int* barred, float* pos_w, double* pg, double* kl, int* n_clip, float* ratio_max, int* valid, int* n_tok, double* row_adv,
+                    int* row_n, double* row_tok, float* loss, svpc_stream_t stream);
+/* svpc_seq_nll_bwd with a weight per position: pos_w (n_cap, lt − 1) fp32 stands where row_w[r] stands, dead (n_cap,) int32 where barred
+ * does (a dead caption's rows are zero).  One launch, every element of dscores written; with pos_w[r, :] = row_w[r] and dead = barred the
+ * bits of svpc_seq_nll_bwd. */
+int svpc_seq_pos_bwd(const float* scores, int ld, const int* row_c, int max_c, const int* tgt, const int* len, const int* dead,
+                     const float* pos_w, const float* dl, int n_cap, int lt, int logits, int unk, float* dscores, int ld_out,
+                     svpc_stream_t stream);
+/* the candidates' advantages from their rewards, per video over its candidates with a finite reward in ascending c (the others get 0):
+ * rule 0 (grpo) (r − mean) / (std + eps) with the population std, 1 (center) r − mean, 2 (rloo) r − the mean of the other finite rewards
+ * (svpc_scst_weights' leave-one-out rule, unscaled).  Fewer than two finite rewards, or the largest equal to the smallest: every advantage
+ * exactly 0 (a test, not arithmetic).  reward / adv (n_vid, k) fp64; 1 <= k <= 16; eps finite and >= 0.  One launch. */
+int svpc_group_advantage(const double* reward, int n_vid, int k, int rule, double eps, double* adv, svpc_stream_t stream);
+
 /* rows between storage kinds in one launch (data movement): dst[r] = convert(src[idx ? idx[r] : r]); kinds 0 fp32, 1 bf16, 2 split (two bf16
  * planes, the lo plane lo_* columns behind the hi plane).  Where rows join or leave an activation stream: the decoder's memory rows
  * (src/rtransformer/model.py:939-947) entering the split stream, its output leaving it (:1086), the [CLS] rows of the clip stream (:1062-1064). */

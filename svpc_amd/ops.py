@@ -4129,3 +4129,167 @@ def seq_pref(scores, row_c, tgt, length, cost, vid_off, ref_cum, row_w, logits, 
     params = tuple(float(v) for v in (beta, gamma, label_smoothing, length_beta, pref_weight))
     return _SeqPref.apply(_c(scores), rc.dev(scores.device) if R else None, tgt, length, _c(cost), off.dev(scores.device), ref_cum, row_w,
                           1 if logits else 0, int(unk_id), max_c, params, (kind, mode))
+
+
+# ------------------------------------------------------------------------------------------------ clipped policy-gradient training
+PG_MAX = RISK_MAX               # candidates per sentence: one lane each (svpc_seq_pg_fwd)
+PG_NORMS = ("sequence", "token", "none")
+PG_ADVANTAGES = ("grpo", "center", "rloo")
+
+
+def _pg_number(name, v, ok, what):
+    if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or not ok(v)):
+        raise ValueError("%s must be %s, got %r" % (name, what, v))
+
+
+def check_pg(k=None, adv=None, vid_off=None, n_sent=None, old_step=None, ref_step=None, rows=None, lt=None, clip_lo=None, clip_hi=None,
+             dual_clip=None, kl_beta=None, norm=None, advantage=None, eps=None, has_ref=None, source=None, utility=None, device=None):
+    """Host checks of clipped policy-gradient training (ValueError for each): ``k`` / ``vid_off`` / ``n_sent`` / ``source``
+    / ``utility`` as ``check_risk`` takes them, ``adv`` as it takes ``cost`` (float64 (N, K)); ``clip_lo`` finite in [0, 1); ``clip_hi``
+    and ``kl_beta`` finite and not negative; ``dual_clip`` 0 (off) or finite and > 1; ``norm`` one of sequence / token / none;
+    ``advantage`` one of grpo / center / rloo; ``eps`` finite and not negative; ``old_step`` / ``ref_step`` contiguous fp32 tensors of
+    ``rows``·(``lt`` − 1) elements (on ``device``, when given); ``kl_beta`` > 0 without a reference (``has_ref`` False, or ``rows`` given
+    and no ``ref_step``).  ``SvpcKernelError`` for an adv, old_step or ref_step that is not on the GPU (no CPU fallback exists).  → (K, N,
+    the utility's column or None, the norm's index or None, the advantage rule's index or None)."""
+    _pg_number("clip_lo", clip_lo, lambda v: 0 <= v < 1, "a finite number in [0, 1)")
+    _pg_number("clip_hi", clip_hi, lambda v: v >= 0, "a finite number >= 0")
+    _pg_number("dual_clip", dual_clip, lambda v: v == 0 or v > 1, "0 (off) or a finite number > 1")
+    _pg_number("kl_beta", kl_beta, lambda v: v >= 0, "a finite number >= 0")
+    _pg_number("eps", eps, lambda v: v >= 0, "a finite number >= 0")
+    if norm is not None and norm not in PG_NORMS:
+        raise ValueError("norm must be one of %s, got %r" % (", ".join(PG_NORMS), norm))
+    if advantage is not None and advantage not in PG_ADVANTAGES:
+        raise ValueError("advantage must be one of %s, got %r" % (", ".join(PG_ADVANTAGES), advantage))
+    if has_ref is None and rows is not None:
+        has_ref = ref_step is not None
+    if kl_beta and has_ref is False:
+        raise ValueError("kl_beta = %r needs the reference model's step scores (ref_step)" % (kl_beta,))
+    for name, t in (("old_step", old_step), ("ref_step", ref_step)):
+        if t is None:
+            continue
+        want = None if rows is None or lt is None else rows * (lt - 1)
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or (want is not None and t.numel() != want):
+            raise ValueError("%s must be contiguous fp32 of %s elements (one per caption row and scored position), got %s"
+                             % (name, want, "%s %s" % (tuple(t.shape), t.dtype) if torch.is_tensor(t) else type(t).__name__))
+        if device is not None and t.device != device:
+            raise ValueError("%s must be on the scores' device %s, got %s" % (name, device, t.device))
+    if adv is not None and (not torch.is_tensor(adv) or adv.dim() != 2 or adv.dtype != torch.float64):
+        raise ValueError("adv must be float64 (N, K), got %s"
+                         % ("%s %s" % (tuple(adv.shape), adv.dtype) if torch.is_tensor(adv) else type(adv).__name__))
+    try:
+        K, N, col = check_risk(k=k, cost=adv, vid_off=vid_off, n_sent=n_sent, source=source, utility=utility, device=device)
+    except ValueError as e:
+        raise ValueError(str(e).replace("cost", "adv").replace("risk training", "policy-gradient training"))
+    except _lib.SvpcKernelError:
+        raise _lib.SvpcKernelError("svpc_amd.ops: policy-gradient training runs on the GPU only (no CPU fallback exists)")
+    for t in (old_step, ref_step):
+        if t is not None and not t.is_cuda:
+            raise _lib.SvpcKernelError("svpc_amd.ops: policy-gradient training runs on the GPU only (no CPU fallback exists)")
+    return (K, N, col, None if norm is None else PG_NORMS.index(norm), None if advantage is None else PG_ADVANTAGES.index(advantage))
+
+
+def group_advantage(reward, rule="grpo", eps=1e-6):
+    """The candidates' advantages from their rewards (svpc_group_advantage, one launch, no read-back): ``reward`` (N, K)
+    float64 → adv (N, K) float64, per video over its candidates with a finite reward in ascending k (the others get 0): ``rule`` "grpo"
+    (r − mean) / (std + ``eps``) with the population std, "center" r − mean, "rloo" r − the mean of the other finite rewards
+    (``scst_weights``' leave-one-out rule, unscaled).  With fewer than two finite rewards, or the largest equal to the smallest, every
+    advantage of the video is exactly 0."""
+    if not torch.is_tensor(reward) or reward.dim() != 2 or reward.dtype != torch.float64:
+        raise ValueError("group_advantage: reward must be float64 (N, K)")
+    N, K = reward.shape
+    _, _, _, _, r = check_pg(k=K, advantage=rule, eps=eps)
+    _need_gpu(reward)
+    reward = _c(reward)
+    adv = torch.empty(N, K, dtype=torch.float64, device=reward.device)
+    _lib.call("group_advantage", _p(reward), N, K, r, float(eps), _p(adv), _stream())
+    return adv
+
+
+class _SeqPg(Function):
+    @staticmethod
+    def forward(ctx, scores, rc, tgt, length, adv, off, old_step, ref_step, row_w, logits, unk_id, max_c, params, norm):
+        R, lt = tgt.shape
+        N, K = adv.shape
+        dev = scores.device
+        step = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        cum = torch.empty(R, dtype=torch.float32, device=dev)
+        barred = torch.empty(R, dtype=torch.int32, device=dev)
+        pos_w = torch.empty(R, lt - 1, dtype=torch.float32, device=dev)
+        pg = torch.empty(R, dtype=torch.float64, device=dev)
+        kl = torch.empty(R, dtype=torch.float64, device=dev)
+        n_clip = torch.empty(R, 2, dtype=torch.int32, device=dev)
+        ratio_max = torch.empty(R, dtype=torch.float32, device=dev)
+        valid = torch.empty(N, K, dtype=torch.int32, device=dev)
+        n_tok = torch.empty(1, dtype=torch.int32, device=dev)
+        row_f = torch.empty(2, R, dtype=torch.float64, device=dev)           # (the launches' own tables: row_adv, row_tok)
+        row_n = torch.empty(R, dtype=torch.int32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _lib.call("seq_pg_fwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(row_w), _p(adv), _p(old_step),
+                  _p(ref_step), _p(off), N, R // K, K, lt, logits, unk_id, *params, norm, _p(step), _p(cum), _p(barred), _p(pos_w), _p(pg),
+                  _p(kl), _p(n_clip), _p(ratio_max), _p(valid), _p(n_tok), _p(row_f[0]), _p(row_n), _p(row_f[1]), _p(loss), _stream())
+        ctx.save_for_backward(scores, rc, tgt, length, barred, pos_w)
+        ctx.cfg = (R, lt, logits, unk_id, max_c)
+        ctx.mark_non_differentiable(cum, step, barred, pos_w, pg, kl, n_clip, ratio_max, valid, n_tok)
+        ctx.set_materialize_grads(False)
+        return loss, cum, step, barred, pos_w, pg, kl, n_clip, ratio_max, valid, n_tok
+
+    @staticmethod
+    def backward(ctx, dl, *_):
+        if dl is None:
+            return (None,) * 14
+        scores, rc, tgt, length, barred, pos_w = ctx.saved_tensors
+        R, lt, logits, unk_id, max_c = ctx.cfg
+        dl = _c(dl.to(torch.float32))
+        dscores = torch.empty(scores.shape, dtype=torch.float32, device=scores.device)     # (every element is written by the kernel)
+        if scores.shape[0] > R * lt:
+            dscores[R * lt:].zero_()
+        # the objective's derivative in step[r, i] is −pos_w[r, i] on every caption that is not barred
+        _lib.call("seq_pos_bwd", _p(scores), scores.stride(0), _p(rc), max_c, _p(tgt), _p(length), _p(barred), _p(pos_w), _p(dl), R, lt,
+                  logits, unk_id, _p(dscores), dscores.shape[1], _stream())
+        return (dscores,) + (None,) * 13
+
+
+def seq_pg(scores, row_c, tgt, length, adv, vid_off, old_step, ref_step, row_w, logits, unk_id, clip_lo=0.2, clip_hi=0.2, dual_clip=0.0,
+           kl_beta=0.0, norm="sequence", max_cols=None):
+    """``seq_nll`` plus the clipped policy-gradient term over every video's K candidate paragraphs (svpc_seq_pg_fwd / svpc_seq_pos_bwd;
+    DESIGN §11.22), differentiable in ``scores`` only: caption row r = t·K + k, ``adv`` (N, K) float64 the candidates' advantages (a
+    non-finite one takes its candidate out), ``vid_off`` as ``seq_risk`` takes it, ``old_step`` / ``ref_step`` (R, Lt − 1) fp32 the
+    behaviour policy's and the frozen reference model's step scores of the same captions (a non-finite entry at a scored position takes
+    its candidate out; no ``old_step``: the ratio is exactly 1; no ``ref_step``: no KL term), ``row_w`` (R,) fp32 the captions'
+    likelihood weights (None: zeros), the rest as ``seq_nll`` takes it.  Per scored position of a valid candidate: ρ = exp(step −
+    old_step), sur = min(ρ·A, clamp(ρ, 1 − ``clip_lo``, 1 + ``clip_hi``)·A), under ``dual_clip`` = c > 1 and A < 0 max(sur, c·A); kl =
+    exp(δ) − δ − 1 with δ = ref_step − step; tok = −sur + ``kl_beta``·kl, divided by N·K·n (``norm`` "sequence", n the candidate's scored
+    positions), by the scored positions of all valid candidates ("token") or by N·K ("none").  → (loss () fp32 = −Σ w_r·cum_r + Σ tok /
+    den, cum, step, barred as ``seq_nll`` returns them — the same bits —, pos_w (R, Lt − 1) fp32: the weight per position under which
+    ``seq_nll``'s gradient is this loss's, pg / kl (R,) float64 the rows' sums of −sur and kl, n_clip (R, 2) int32 the positions clipped
+    from above / from below, ratio_max (R,) fp32, valid (N, K) int32, n_tok (1,) int32).  With every advantage 0 and ``kl_beta`` = 0 the
+    loss and its gradient have ``seq_nll``'s bits."""
+    if tgt.dim() != 2 or tgt.shape[1] < 2 or not _id_rows(tgt, tgt.shape[0], tgt.shape[1], scores.device):
+        raise ValueError("seq_pg: tgt must be a contiguous int32 (R, Lt >= 2) matrix on the scores' device")
+    R, lt = tgt.shape
+    if scores.dim() != 2 or scores.shape[0] < R * lt or scores.dtype != torch.float32:
+        raise ValueError("seq_pg: scores must be fp32 (>= R·Lt, C) rows")
+    if not _row_vec(length, R, torch.int32, scores.device):
+        raise ValueError("seq_pg: length must be contiguous int32 (R,) on the scores' device")
+    K, N, _, kind, _ = check_pg(adv=adv, old_step=old_step, ref_step=ref_step, rows=R, lt=lt, clip_lo=clip_lo, clip_hi=clip_hi,
+                                dual_clip=dual_clip, kl_beta=kl_beta, norm=norm, device=scores.device)
+    if kind is None or K is None:
+        raise ValueError("seq_pg: adv must be float64 (N, K) and norm one of %s" % ", ".join(PG_NORMS))
+    if R % K:
+        raise ValueError("seq_pg: %d caption rows are no multiple of the K = %d candidates per sentence" % (R, K))
+    off = as_idx(vid_off)
+    check_pg(adv=adv, vid_off=off, n_sent=R // K)
+    if row_w is None:
+        row_w = torch.zeros(R, dtype=torch.float32, device=scores.device)
+    elif not torch.is_tensor(row_w) or not _row_vec(row_w, R, torch.float32, scores.device):
+        raise ValueError("seq_pg: row_w must be contiguous fp32 (R,) on the scores' device")
+    rc = as_idx(row_c)
+    if len(rc.host) != R:
+        raise ValueError("seq_pg: one column count per caption row (%d), got %d" % (R, len(rc.host)))
+    max_c = int(max_cols) if max_cols is not None else (max(rc.host) if R else 1)
+    if max_c > scores.shape[1] or (R and (min(rc.host) < 1 or max(rc.host) > max_c)):
+        raise ValueError("seq_pg: rows of 1..%d columns, inside the score matrix and max_cols" % scores.shape[1])
+    _need_gpu(scores)
+    params = tuple(float(v) for v in (clip_lo, clip_hi, dual_clip, kl_beta))
+    return _SeqPg.apply(_c(scores), rc.dev(scores.device) if R else None, tgt, length, _c(adv), off.dev(scores.device), old_step, ref_step,
+                        row_w, 1 if logits else 0, int(unk_id), max_c, params, kind)
