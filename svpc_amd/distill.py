@@ -15,7 +15,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .scst import graded_pass
+from .scst import eval_mode, fresh_inputs, graded_pass, loss_result, per_token, row_weights as _fp32_rows
 from .synthetic import UNK
 
 AGREE = ("model_mode", "vocab_size", "max_t_len", "max_v_len", "max_i_len", "video_feature_size")
@@ -31,31 +31,6 @@ def _check_pair(translator, teacher):
     devs = [next(m.parameters()).device for m in (translator.model, teacher.model)]
     if devs[0] != devs[1]:
         raise ValueError("distillation: student and teacher differ in device: %s against %s" % (devs[0], devs[1]))
-
-
-def _fresh(model, inputs):
-    """the inputs with copies of the ids and masks: a decode or a forced pass blanks their text half in place"""
-    dec_in = list(inputs)
-    dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-    dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
-    return dec_in
-
-
-class _Eval(object):
-    """the teacher's models in eval mode, their modes restored afterwards (the teacher may be the student's own translator)"""
-
-    def __init__(self, teacher):
-        self.models = list(teacher._members())
-
-    def __enter__(self):
-        self.was = [m for m in self.models if m.training]      # (a member already in eval mode is left alone: walking a model's modules
-        for m in self.was:                                      # twice per member and step is host time the eager passes do not hide)
-            m.eval()
-
-    def __exit__(self, *exc):
-        for m in self.was:
-            m.train(True)
-        return False
 
 
 def _graded(translator, teacher, model_inputs, dec_seq_list, row_weights, who, check=None, kd_check=None):
@@ -75,8 +50,8 @@ def _graded(translator, teacher, model_inputs, dec_seq_list, row_weights, who, c
         ops.check_distill(kd_weights=kd_check, shape=tuple(ids.shape[:2]))
     if inputs[1][0].device.type != "cuda":
         raise ops._lib.SvpcKernelError("%s runs on the GPU only (no CPU fallback exists)" % who)
-    with _Eval(teacher):
-        t = teacher.teacher_scores(_fresh(teacher.model, inputs), dec_seq_list)
+    with eval_mode(teacher._members()):
+        t = teacher.teacher_scores(fresh_inputs(teacher.model, inputs), dec_seq_list)
 
     def head(p):
         T, K, Lt = p.T, p.K, p.Lt
@@ -85,9 +60,8 @@ def _graded(translator, teacher, model_inputs, dec_seq_list, row_weights, who, c
         w, v = row_weights(p)
         loss, cum, step, barred, kd, kdstep, ent, hstep = ops.seq_kd(p.scores, p.cap_c, p.tgt, p.length, t.scores, w, v, p.logits, t.logits,
                                                                      UNK, max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), kd=kd.view(T, K), ent=ent.view(T, K), kdstep=kdstep.view(T, K, Lt - 1),
-                               hstep=hstep.view(T, K, Lt - 1))
+        return loss_result(p, loss, cum, step, barred, kd=kd.view(T, K), ent=ent.view(T, K), kdstep=kdstep.view(T, K, Lt - 1),
+                           hstep=hstep.view(T, K, Lt - 1))
     return graded_pass(translator, inputs, dec_seq_list, check, head, who=who)
 
 
@@ -103,7 +77,7 @@ def distillation_loss(translator, teacher, model_inputs, dec_seq_list, weights, 
             raise ValueError("distillation_loss: weights and kd_weights must be floating point tensors")
 
     def row_weights(p):
-        return tuple(t.detach().reshape(-1).to(torch.float32).contiguous() for t in (weights, kd_weights))
+        return tuple(_fp32_rows(t) for t in (weights, kd_weights))
     return _graded(translator, teacher, model_inputs, dec_seq_list, row_weights, "distillation_loss", check=weights, kd_check=kd_weights)
 
 
@@ -117,10 +91,8 @@ class Distill(object):
 
     @staticmethod
     def _per_token(p, alpha):
-        """w_r = (1 − α) / n, v_r = α / n, n = max(1, Σ len) formed on the device in fp64 and rounded once; no read-back"""
-        n = p.length.sum(dtype=torch.int64).clamp_(min=1).to(torch.float64)
-        R = p.length.shape[0]
-        return tuple((c / n).to(torch.float32).expand(R).contiguous() for c in (1.0 - float(alpha), float(alpha)))
+        """w_r = (1 − α) / n, v_r = α / n (``scst.per_token``)"""
+        return per_token(p, 1.0 - float(alpha), float(alpha))
 
     def word_step(self, model_inputs, input_labels_list, alpha=0.5):
         """Word-level distillation on the batch's gold captions (``Translator.gold_captions``): loss = ((1 − α)·Σ −cum + α·Σ kd) / n over
@@ -147,8 +119,8 @@ class Distill(object):
         if unknown:
             raise TypeError("unknown keyword(s): %s" % ", ".join(sorted(unknown)))
         inputs = list(model_inputs)
-        with _Eval(te):
-            dec_in = _fresh(te.model, inputs)
+        with eval_mode(te._members()):
+            dec_in = fresh_inputs(te.model, inputs)
             if source == "beam":
                 kw = dict(decode_kw)
                 beam = kw.pop("beam_size", None)

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .ops_common import Idx
-from .scst import graded_pass
+from .scst import PhaseEvents, eval_mode, fresh_inputs, graded_pass, loss_result, row_weights
 from .synthetic import UNK
 
 LOSS_KW = ("alpha", "length_beta", "margin", "risk_weight", "rank_weight", "weights")
@@ -46,18 +46,15 @@ def risk_loss(translator, model_inputs, dec_seq_list, cost, alpha=5e-3, length_b
     ops.check_risk(cost=cost, alpha=alpha, length_beta=length_beta, margin=margin, risk_weight=risk_weight, rank_weight=rank_weight)
 
     def head(p):
-        T, K, Lt = p.T, p.K, p.Lt
-        ops.check_risk(k=K, cost=cost, vid_off=_vid_off(p), n_sent=T)
-        w = None if weights is None else weights.detach().reshape(-1).to(torch.float32).contiguous()
+        ops.check_risk(k=p.K, cost=cost, vid_off=_vid_off(p), n_sent=p.T)
         loss, cum, step, barred, risk, rank, Q, z, valid, w_eff = ops.seq_risk(
-            p.scores, p.cap_c, p.tgt, p.length, cost.detach(), _vid_off(p), w, p.logits, UNK, alpha, length_beta, margin, risk_weight,
-            rank_weight, max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), risk=risk, rank=rank, Q=Q, z=z, valid=valid, w_eff=w_eff.view(T, K))
+            p.scores, p.cap_c, p.tgt, p.length, cost.detach(), _vid_off(p), row_weights(weights), p.logits, UNK, alpha, length_beta, margin,
+            risk_weight, rank_weight, max_cols=p.max_cols)
+        return loss_result(p, loss, cum, step, barred, risk=risk, rank=rank, Q=Q, z=z, valid=valid, w_eff=w_eff.view(p.T, p.K))
     return graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="risk_loss")
 
 
-class MinimumRisk(object):
+class MinimumRisk(PhaseEvents):
     """One minimum-risk / ranking training step over a ``Translator``'s model.  ``corpus`` is the ``ReferenceCorpus`` the
     candidates are scored against (its idf is CIDEr's)."""
 
@@ -65,12 +62,6 @@ class MinimumRisk(object):
         self.translator = translator
         self.corpus = corpus
         self.phase_events = None    # tools/bench_risk.py: a list → ``step`` appends HIP events: start, decoded, rewards, graded forward
-
-    def _stamp(self):
-        if self.phase_events is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            self.phase_events.append(e)
 
     def _decode(self, inputs, source, K, seed, kw):
         """the K candidates per sentence of the named decoder, with ``translate_batch_consensus``' argument rules → (dec, oov)"""
@@ -90,6 +81,24 @@ class MinimumRisk(object):
         if K % G or not 1 <= K // G <= W // G:
             raise ValueError("num_candidates must be num_groups times 1..%d rows per group, got %d with %d groups" % (W // G, K, G))
         return tr.translate_batch_diverse(inputs, W, G, kw.pop("diversity_strength", None), K // G, **kw)[:2]
+
+    def _rollout(self, model_inputs, videos, K, col, source, seed, decode_kw, include_gold=False, input_labels_list=None):
+        """The rollout the candidate-set steps share, after their argument checks: stamp, the decode of K candidates per sentence in eval
+        mode on copies of the ids and masks (the model's mode is restored, also when the decode raises), the gold captions as candidate K
+        when asked, stamp, the candidates' rewards (column ``col`` of ``caption_scores``).  → (dec, oov, K, reward (N, K) float64)."""
+        tr = self.translator
+        model = tr.model
+        self._stamp()
+        with eval_mode([model]):
+            dec, oov = self._decode(fresh_inputs(model, model_inputs), source, K, seed, decode_kw)
+        if include_gold:
+            gold = tr.gold_captions(input_labels_list, model_inputs[11])
+            dec = [torch.cat([d, g.unsqueeze(1).to(d.dtype)], 1) for d, g in zip(dec, gold)]
+            K += 1
+        self._stamp()
+        plan = self.corpus.plan(list(videos))
+        reward = torch.stack([tr.caption_scores(dec, plan, row=k)[:, col] for k in range(K)], 1).contiguous()
+        return dec, oov, K, reward
 
     def step(self, model_inputs, videos, num_candidates=4, source="stochastic", utility="CIDEr", include_gold=False, input_labels_list=None,
              seed=None, **loss_and_decode_kw):
@@ -115,27 +124,9 @@ class MinimumRisk(object):
             ops.check_risk(k=K + 1)
         loss_kw = {k: loss_and_decode_kw.pop(k) for k in LOSS_KW if k in loss_and_decode_kw}
         ops.check_risk(**{k: v for k, v in loss_kw.items() if k != "weights"})
-        model = tr.model
-        was_training = model.training
-        inputs = list(model_inputs)
+        dec, oov, K, reward = self._rollout(model_inputs, videos, K, col, source, seed, loss_and_decode_kw, include_gold, input_labels_list)
         self._stamp()
-        model.eval()
-        try:
-            dec_in = list(inputs)
-            dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-            dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
-            dec, oov = self._decode(dec_in, source, K, seed, loss_and_decode_kw)
-        finally:
-            model.train(was_training)
-        if include_gold:
-            gold = tr.gold_captions(input_labels_list, model_inputs[11])
-            dec = [torch.cat([d, g.unsqueeze(1).to(d.dtype)], 1) for d, g in zip(dec, gold)]
-            K += 1
-        self._stamp()
-        plan = self.corpus.plan(list(videos))
-        reward = torch.stack([tr.caption_scores(dec, plan, row=k)[:, col] for k in range(K)], 1).contiguous()
-        self._stamp()
-        r = risk_loss(tr, inputs, dec, -reward, **loss_kw)
+        r = risk_loss(tr, list(model_inputs), dec, -reward, **loss_kw)
         self._stamp()
         return SimpleNamespace(loss=r.loss, reward=reward, expected_reward=-r.risk, risk=r.risk, rank=r.rank, Q=r.Q, w_eff=r.w_eff, cum=r.cum,
                                barred=r.barred, dec_seq_list=dec, oov_word_dict=oov)

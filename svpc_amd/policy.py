@@ -16,11 +16,9 @@ steps: ``PolicyOptimization.collect`` decodes, rewards and scores once, ``update
 between.  The caller runs ``graph.backward_all(model, loss)``, ``ops.join_side()`` and the optimizer, as for ``mrt.MinimumRisk``."""
 from types import SimpleNamespace
 
-import torch
-
 from . import ops
 from .mrt import MinimumRisk, _vid_off
-from .scst import graded_pass
+from .scst import frozen_scores, graded_pass, loss_result, row_weights
 from .synthetic import UNK
 
 LOSS_KW = ("clip_lo", "clip_hi", "dual_clip", "kl_beta", "norm", "weights")
@@ -33,20 +31,7 @@ def position_scores(scorer, model_inputs, dec_seq_list):
     without gradients in eval mode (the previous mode is restored) on copies of the ids and masks (``score_captions`` blanks their text
     half in place), and the result is a clone: with ``graph=True`` the pass's own buffer belongs to a captured graph and the next replay
     overwrites it.  −inf marks a position the scorer bars.  No host synchronisation beyond ``score_captions``'."""
-    models = list(scorer._members())
-    was = [m for m in models if m.training]         # (a member already in eval mode is left alone: no walk over its modules)
-    inputs = list(model_inputs)
-    stacked = models[0]._stacked
-    inputs[0] = list(stacked(list(inputs[0])).clone().unbind(0))
-    inputs[2] = list(stacked(list(inputs[2])).clone().unbind(0))
-    for m in was:
-        m.eval()
-    try:
-        with torch.no_grad():
-            return scorer.score_captions(inputs, dec_seq_list).step.clone()
-    finally:
-        for m in was:
-            m.train(True)
+    return frozen_scores(scorer, model_inputs, dec_seq_list, "step")
 
 
 def policy_loss(translator, model_inputs, dec_seq_list, adv, old_step=None, ref_step=None, clip_lo=0.2, clip_hi=0.2, dual_clip=0.0,
@@ -67,14 +52,12 @@ def policy_loss(translator, model_inputs, dec_seq_list, adv, old_step=None, ref_
     def head(p):
         T, K, Lt = p.T, p.K, p.Lt
         ops.check_pg(k=K, adv=adv, vid_off=_vid_off(p), n_sent=T)
-        w = None if weights is None else weights.detach().reshape(-1).to(torch.float32).contiguous()
         loss, cum, step, barred, pos_w, pg, kl, n_clip, ratio_max, valid, n_tok = ops.seq_pg(
             p.scores, p.cap_c, p.tgt, p.length, adv.detach(), _vid_off(p), None if old_step is None else old_step.detach(),
-            None if ref_step is None else ref_step.detach(), w, p.logits, UNK, clip_lo, clip_hi, dual_clip, kl_beta, norm,
+            None if ref_step is None else ref_step.detach(), row_weights(weights), p.logits, UNK, clip_lo, clip_hi, dual_clip, kl_beta, norm,
             max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), pos_w=pos_w.view(T, K, Lt - 1), pg=pg.view(T, K), kl=kl.view(T, K),
-                               n_clip=n_clip.view(T, K, 2), ratio_max=ratio_max.view(T, K), valid=valid, n_tok=n_tok)
+        return loss_result(p, loss, cum, step, barred, pos_w=pos_w.view(T, K, Lt - 1), pg=pg.view(T, K), kl=kl.view(T, K),
+                           n_clip=n_clip.view(T, K, 2), ratio_max=ratio_max.view(T, K), valid=valid, n_tok=n_tok)
     return graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="policy_loss")
 
 
@@ -107,22 +90,8 @@ class PolicyOptimization(MinimumRisk):
         tr = self.translator
         K, _, col, _, _ = ops.check_pg(k=num_candidates, source=source, utility=utility, advantage=advantage, eps=adv_eps)
         self._refuse_self_reference()
-        model = tr.model
-        was_training = model.training
+        dec, oov, K, reward = self._rollout(model_inputs, videos, K, col, source, seed, decode_kw)
         inputs = list(model_inputs)
-        decode_kw = dict(decode_kw)
-        self._stamp()
-        model.eval()
-        try:
-            dec_in = list(inputs)
-            dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-            dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
-            dec, oov = self._decode(dec_in, source, K, seed, decode_kw)
-        finally:
-            model.train(was_training)
-        self._stamp()
-        plan = self.corpus.plan(list(videos))
-        reward = torch.stack([tr.caption_scores(dec, plan, row=k)[:, col] for k in range(K)], 1).contiguous()
         adv = ops.group_advantage(reward, advantage, adv_eps)
         self._stamp()
         old_step = None if on_policy else position_scores(tr, inputs, dec)

@@ -16,11 +16,9 @@ so ``ops.seq_pref`` forms them on the device in the forward (``w_eff``) and its 
 runs ``graph.backward_all(model, loss)``, ``ops.join_side()`` and the optimizer, as for ``mrt.MinimumRisk``."""
 from types import SimpleNamespace
 
-import torch
-
 from . import ops
 from .mrt import MinimumRisk, _vid_off
-from .scst import graded_pass
+from .scst import frozen_scores, graded_pass, loss_result, row_weights
 from .synthetic import UNK
 
 LOSS_KW = ("beta", "gamma", "label_smoothing", "length_beta", "pref_weight", "loss_type", "pairs", "weights")
@@ -32,20 +30,7 @@ def reference_scores(reference, model_inputs, dec_seq_list):
     pass runs without gradients in eval mode (the previous mode is restored) on copies of the ids and masks (``score_captions`` blanks
     their text half in place), and the result is a clone: with ``graph=True`` the pass's own buffer belongs to a captured graph and the
     next replay overwrites it.  −inf marks a caption the reference bars.  No host synchronisation beyond ``score_captions``'."""
-    models = list(reference._members())
-    was = [m for m in models if m.training]         # (a member already in eval mode is left alone: no walk over its modules)
-    inputs = list(model_inputs)
-    stacked = models[0]._stacked
-    inputs[0] = list(stacked(list(inputs[0])).clone().unbind(0))
-    inputs[2] = list(stacked(list(inputs[2])).clone().unbind(0))
-    for m in was:
-        m.eval()
-    try:
-        with torch.no_grad():
-            return reference.score_captions(inputs, dec_seq_list).cum.clone()
-    finally:
-        for m in was:
-            m.train(True)
+    return frozen_scores(reference, model_inputs, dec_seq_list, "cum")
 
 
 def preference_loss(translator, model_inputs, dec_seq_list, cost, ref_cum=None, beta=0.1, gamma=0.0, label_smoothing=0.0, length_beta=0.0,
@@ -65,16 +50,13 @@ def preference_loss(translator, model_inputs, dec_seq_list, cost, ref_cum=None, 
                    loss_type=loss_type, pairs=pairs)
 
     def head(p):
-        T, K, Lt = p.T, p.K, p.Lt
-        ops.check_pref(k=K, cost=cost, vid_off=_vid_off(p), n_sent=T)
-        w = None if weights is None else weights.detach().reshape(-1).to(torch.float32).contiguous()
+        ops.check_pref(k=p.K, cost=cost, vid_off=_vid_off(p), n_sent=p.T)
         rc = None if ref_cum is None else ref_cum.detach().reshape(-1)
         loss, cum, step, barred, pref, reward, valid, n_pairs, n_correct, margin, w_eff = ops.seq_pref(
-            p.scores, p.cap_c, p.tgt, p.length, cost.detach(), _vid_off(p), rc, w, p.logits, UNK, beta, gamma, label_smoothing, length_beta,
-            pref_weight, loss_type, pairs, max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), pref=pref, reward=reward, valid=valid, n_pairs=n_pairs, n_correct=n_correct,
-                               margin=margin, w_eff=w_eff.view(T, K))
+            p.scores, p.cap_c, p.tgt, p.length, cost.detach(), _vid_off(p), rc, row_weights(weights), p.logits, UNK, beta, gamma,
+            label_smoothing, length_beta, pref_weight, loss_type, pairs, max_cols=p.max_cols)
+        return loss_result(p, loss, cum, step, barred, pref=pref, reward=reward, valid=valid, n_pairs=n_pairs, n_correct=n_correct,
+                           margin=margin, w_eff=w_eff.view(p.T, p.K))
     return graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="preference_loss")
 
 
@@ -112,25 +94,9 @@ class PreferenceOptimization(MinimumRisk):
         model = tr.model
         if self.reference is tr and model.training:
             raise ValueError("the reference is the policy's own translator and its model is in training mode: the reference would see dropout")
-        was_training = model.training
+        dec, oov, K, reward = self._rollout(model_inputs, videos, K, col, source, seed, loss_and_decode_kw, include_gold, input_labels_list)
+        self._stamp()
         inputs = list(model_inputs)
-        self._stamp()
-        model.eval()
-        try:
-            dec_in = list(inputs)
-            dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-            dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
-            dec, oov = self._decode(dec_in, source, K, seed, loss_and_decode_kw)
-        finally:
-            model.train(was_training)
-        if include_gold:
-            gold = tr.gold_captions(input_labels_list, model_inputs[11])
-            dec = [torch.cat([d, g.unsqueeze(1).to(d.dtype)], 1) for d, g in zip(dec, gold)]
-            K += 1
-        self._stamp()
-        plan = self.corpus.plan(list(videos))
-        reward = torch.stack([tr.caption_scores(dec, plan, row=k)[:, col] for k in range(K)], 1).contiguous()
-        self._stamp()
         ref_cum = None if self.reference is None else reference_scores(self.reference, inputs, dec)
         self._stamp()
         r = preference_loss(tr, inputs, dec, -reward, ref_cum=ref_cum, **loss_kw)

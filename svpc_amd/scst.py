@@ -51,6 +51,73 @@ def _force_plan(model, plan, K, dicts, c_list, dev):
     return fp
 
 
+def fresh_inputs(model, inputs):
+    """the inputs with copies of the ids and masks (slots 0 and 2): a decode or a forced pass blanks their text half in place"""
+    dec_in = list(inputs)
+    dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
+    dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
+    return dec_in
+
+
+class eval_mode(object):
+    """``models`` (a translator's ``_members()``, or its one model) in eval mode, and those it switched back in training mode afterwards,
+    also when the body raises.  A member already in eval mode is left alone: walking a model's modules twice per member and step is host
+    time the eager passes do not hide."""
+
+    def __init__(self, models):
+        self.models = list(models)
+
+    def __enter__(self):
+        self.was = [m for m in self.models if m.training]
+        for m in self.was:
+            m.eval()
+
+    def __exit__(self, *exc):
+        for m in self.was:
+            m.train(True)
+        return False
+
+
+def frozen_scores(scorer, model_inputs, dec_seq_list, field):
+    """``scorer.score_captions(model_inputs, dec_seq_list).<field>`` of a frozen scorer, any ``Translator``, as a tensor of its own:
+    without gradients, its members in eval mode (``eval_mode``), on copies of the ids and masks (``fresh_inputs``).  The result is a
+    clone: with ``graph=True`` the pass's own buffer belongs to a captured graph and the next replay overwrites it."""
+    models = list(scorer._members())
+    inputs = fresh_inputs(models[0], model_inputs)
+    with eval_mode(models), torch.no_grad():
+        return getattr(scorer.score_captions(inputs, dec_seq_list), field).clone()
+
+
+def row_weights(weights):
+    """a head's optional per-caption weights (T, K) or (T·K,) → fp32 (T·K,) without a gradient, or None"""
+    return None if weights is None else weights.detach().reshape(-1).to(torch.float32).contiguous()
+
+
+def loss_result(p, loss, cum, step, barred, **own):
+    """what every head over ``graded_pass`` returns: ``sequence_loss``'s namespace in its (T, K) views plus the head's ``own`` fields"""
+    return SimpleNamespace(loss=loss, cum=cum.view(p.T, p.K), step=step.view(p.T, p.K, p.Lt - 1), barred=barred.view(p.T, p.K),
+                           length=p.length.view(p.T, p.K), **own)
+
+
+def per_token(p, *coefficients):
+    """c / n per coefficient as an fp32 (R,) vector, n = max(1, Σ len) formed on the device in fp64 and rounded once; no read-back"""
+    n = p.length.sum(dtype=torch.int64).clamp_(min=1).to(torch.float64)
+    R = p.length.shape[0]
+    return tuple((c / n).to(torch.float32).expand(R).contiguous() for c in coefficients)
+
+
+class PhaseEvents(object):
+    """``phase_events``: None, or a list to which ``_stamp`` appends a HIP event at each phase boundary of a step (the tools/bench_*
+    scripts time the phases with them)"""
+    phase_events = None
+
+    def _stamp(self):
+        if self.phase_events is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.phase_events.append(e)
+
+
 def graded_pass(translator, model_inputs, dec_seq_list, weights, head, who="sequence_loss"):
     """The graded forced pass up to the decoder's score matrix, then ``head``: the encoder side of the decode and the decoder once over all
     positions of the T·K given captions, with gradients.  ``head`` is called inside the pass's ``enable_grad`` with a namespace — ``scores``
@@ -137,14 +204,11 @@ def sequence_loss(translator, model_inputs, dec_seq_list, weights):
     ``model.eval()``: deterministic.  → a namespace: ``loss`` () fp32 (the only result with a gradient), ``cum`` (T, K) fp32, ``step``
     (T, K, Lt − 1) fp32, ``barred`` (T, K) int32, ``length`` (T, K) int32.  No host synchronisation beyond the batch structure's tables."""
     def head(p):
-        w = weights.detach().reshape(-1).to(torch.float32).contiguous()
-        loss, cum, step, barred = ops.seq_nll(p.scores, p.cap_c, p.tgt, p.length, w, p.logits, UNK, max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(p.T, p.K), step=step.view(p.T, p.K, p.Lt - 1), barred=barred.view(p.T, p.K),
-                               length=p.length.view(p.T, p.K))
+        return loss_result(p, *ops.seq_nll(p.scores, p.cap_c, p.tgt, p.length, row_weights(weights), p.logits, UNK, max_cols=p.max_cols))
     return graded_pass(translator, model_inputs, dec_seq_list, weights, head)
 
 
-class SelfCritical(object):
+class SelfCritical(PhaseEvents):
     """One self-critical training step over a ``Translator``'s model.  ``corpus`` is the ``ReferenceCorpus`` the rewards are
     scored against (its idf is CIDEr's)."""
 
@@ -153,12 +217,6 @@ class SelfCritical(object):
         self.corpus = corpus
         self._row_vid = {}
         self.phase_events = None    # tools/bench_scst.py: a list → ``step`` appends HIP events: start, sampled, greedy, rewards, graded forward
-
-    def _stamp(self):
-        if self.phase_events is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()
-            self.phase_events.append(e)
 
     def step(self, model_inputs, videos, num_samples=4, baseline="greedy", utility="CIDEr", seed=None, **sampling_kw):
         """``model_inputs`` as ``translate_batch`` takes them, ``videos`` the batch's videos as ``corpus.plan`` takes them → a namespace:
@@ -169,23 +227,13 @@ class SelfCritical(object):
         tr = self.translator
         rule, col, K = ops.check_scst(num_samples=num_samples, baseline=baseline, utility=utility)
         model = tr.model
-        was_training = model.training
         inputs = list(model_inputs)
-        dev = model_inputs[1][0].device
         self._stamp()
-        model.eval()
-        try:
-            def fresh():
-                dec_in = list(inputs)
-                dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-                dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
-                return dec_in
-            dec, oov, _, _ = tr.translate_batch_sample(fresh(), num_samples=K, seed=seed, **sampling_kw)
+        with eval_mode([model]):
+            dec, oov, _, _ = tr.translate_batch_sample(fresh_inputs(model, inputs), num_samples=K, seed=seed, **sampling_kw)
             self._stamp()
-            greedy = tr.translate_batch_greedy(*fresh(), model)[0] if rule == 1 else None
+            greedy = tr.translate_batch_greedy(*fresh_inputs(model, inputs), model)[0] if rule == 1 else None
             self._stamp()
-        finally:
-            model.train(was_training)
         plan = self.corpus.plan(list(videos))
         reward = torch.stack([tr.caption_scores(dec, plan, row=k)[:, col] for k in range(K)], 1).contiguous()
         r_g = tr.caption_scores(greedy, plan)[:, col].contiguous() if rule == 1 else None

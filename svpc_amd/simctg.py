@@ -13,7 +13,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .scst import graded_pass
+from .scst import graded_pass, loss_result, row_weights as _fp32_rows
 from .synthetic import UNK
 
 
@@ -24,8 +24,7 @@ def _graded(translator, model_inputs, dec_seq_list, row_weights, margin, who, ch
         w, v = row_weights(p)
         nll, cum, step, barred = ops.seq_nll(p.scores, p.cap_c, p.tgt, p.length, w, p.logits, UNK, max_cols=p.max_cols)
         con, cl, sim, nact = ops.seq_cl(ops.to_f32(p.hidden), p.length, v, margin, Lt)
-        return SimpleNamespace(loss=nll + con, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), cl=cl.view(T, K), sim=sim.view(T, K), nact=nact.view(T, K))
+        return loss_result(p, nll + con, cum, step, barred, cl=cl.view(T, K), sim=sim.view(T, K), nact=nact.view(T, K))
     return graded_pass(translator, model_inputs, dec_seq_list, check, head, who=who)
 
 
@@ -39,7 +38,7 @@ def contrastive_loss(translator, model_inputs, dec_seq_list, weights, cl_weights
 
     def row_weights(p):
         ops.check_simctg(weights=weights, cl_weights=cl_weights, shape=(p.T, p.K))
-        return tuple(t.detach().reshape(-1).to(torch.float32).contiguous() for t in (weights, cl_weights))
+        return tuple(_fp32_rows(t) for t in (weights, cl_weights))
     return _graded(translator, model_inputs, dec_seq_list, row_weights, margin, "contrastive_loss", check=weights)
 
 

@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .ops_common import Idx
-from .scst import graded_pass
+from .scst import eval_mode, fresh_inputs, graded_pass, loss_result, per_token, row_weights as _fp32_rows
 from .synthetic import EOS, UNK
 
 SOURCES = ("greedy", "sample")
@@ -35,15 +35,14 @@ def _sent_first(p):
 def _graded(translator, model_inputs, dec_seq_list, row_weights, rule, ngram, scope, who, check=None):
     """``row_weights(p)`` → (w, u) fp32 (R,) on the device, from the pass's tables"""
     def head(p):
-        T, K, Lt = p.T, p.K, p.Lt
-        ops.check_unlikelihood(rule, ngram, scope, lt=Lt)
+        T, K = p.T, p.K
+        ops.check_unlikelihood(rule, ngram, scope, lt=p.Lt)
         neg, npen, nrep = ops.ul_negatives(p.tgt, p.length, p.finished, p.cap_c, UNK, EOS, rule, ngram, scope,
                                            sent_first=_sent_first(p) if rule == "ngram" and scope == "paragraph" else None, K=K)
         w, u = row_weights(p)
         loss, cum, step, barred, ul, ulstep = ops.seq_ul(p.scores, p.cap_c, p.tgt, p.length, neg, w, u, p.logits, UNK, max_cols=p.max_cols)
-        return SimpleNamespace(loss=loss, cum=cum.view(T, K), step=step.view(T, K, Lt - 1), barred=barred.view(T, K),
-                               length=p.length.view(T, K), ul=ul.view(T, K), ulstep=ulstep.view(T, K, Lt - 1), npen=npen.view(T, K),
-                               nrep=nrep.view(T, K), weights=w, ul_weights=u)
+        return loss_result(p, loss, cum, step, barred, ul=ul.view(T, K), ulstep=ulstep.view(T, K, p.Lt - 1), npen=npen.view(T, K),
+                           nrep=nrep.view(T, K), weights=w, ul_weights=u)
     return graded_pass(translator, model_inputs, dec_seq_list, check, head, who=who)
 
 
@@ -61,7 +60,7 @@ def unlikelihood_loss(translator, model_inputs, dec_seq_list, weights, ul_weight
 
     def row_weights(p):
         ops.check_unlikelihood(rule, ngram, scope, weights=weights, ul_weights=ul_weights, shape=(p.T, p.K))
-        return tuple(t.detach().reshape(-1).to(torch.float32).contiguous() for t in (weights, ul_weights))
+        return tuple(_fp32_rows(t) for t in (weights, ul_weights))
     r = _graded(translator, model_inputs, dec_seq_list, row_weights, rule, ngram, scope, "unlikelihood_loss", check=weights)
     del r.weights, r.ul_weights
     return r
@@ -75,12 +74,10 @@ class Unlikelihood(object):
 
     @staticmethod
     def _per_token(p, alpha, with_nll):
-        """w_r = 1 / n (or 0), u_r = α / n, n = max(1, Σ len) formed on the device in fp64 and rounded once; no read-back"""
-        n = p.length.sum(dtype=torch.int64).clamp_(min=1).to(torch.float64)
-        R = p.length.shape[0]
-        w = (1.0 / n).to(torch.float32).expand(R).contiguous() if with_nll else torch.zeros(R, dtype=torch.float32, device=n.device)
-        u = (float(alpha) / n).to(torch.float32).expand(R).contiguous()
-        return w, u
+        """w_r = 1 / n (or 0), u_r = α / n (``scst.per_token``)"""
+        if with_nll:
+            return per_token(p, 1.0, float(alpha))
+        return torch.zeros(p.length.shape[0], dtype=torch.float32, device=p.length.device), per_token(p, float(alpha))[0]
 
     def token_step(self, model_inputs, input_labels_list, alpha=1.0):
         """Token-level unlikelihood on the batch's gold captions (``Translator.gold_captions``): loss = (−Σ cum + α·Σ ul) / n over the
@@ -106,19 +103,13 @@ class Unlikelihood(object):
         if unknown:
             raise TypeError("unknown keyword(s): %s" % ", ".join(sorted(unknown)))
         model = tr.model
-        was_training = model.training
         inputs = list(model_inputs)
-        dec_in = list(inputs)
-        model.eval()
-        try:
-            dec_in[0] = list(model._stacked(list(inputs[0])).clone().unbind(0))
-            dec_in[2] = list(model._stacked(list(inputs[2])).clone().unbind(0))
+        with eval_mode([model]):
+            dec_in = fresh_inputs(model, inputs)
             if source == "sample":
                 dec, oov = tr.translate_batch_sample(dec_in, num_samples=1, seed=seed, **sampling_kw)[:2]
             else:
                 with torch.no_grad():
                     dec, oov = tr.translate_batch_greedy(*dec_in, model)[:2]
-        finally:
-            model.train(was_training)
         r = _graded(tr, inputs, dec, lambda p: self._per_token(p, alpha, False), "ngram", ngram, scope, "sequence_step")
         return SimpleNamespace(loss=r.loss, ul=r.ul, npen=r.npen, nrep=r.nrep, dec_seq_list=dec, oov_word_dict=oov)
